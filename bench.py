@@ -19,8 +19,14 @@ Also reported (rank 0):
     implicit GEMM with the GELU epilogue: CNN extractor conv1..5 and the FFN up-projections): algorithmic FLOPs
     per launch / average launch time (HIP events on the launching stream over the timed steps) against the
     f32-equivalent peak of its arithmetic (split-f16: 2516.6 / 3 TFLOP/s; f32 MFMA: 157.3);
-  * cpu_baseline (N = 1 only): the CPU oracle (torch-CPU fp32 modules on the host threads + the C Viterbi) on a
-    bounded sample of the same workload.
+  * with --full, after the timed steps: the secondary kernels' rooflines, the sustained run, the step breakdown,
+    BASELINE configs 3 (N > 1) / 4 / 5 (N = 1), the chunked run's agreement, host file I/O, and cpu_baseline (N = 1
+    only): the CPU oracle (torch-CPU fp32 modules on the host threads + the C Viterbi) on a bounded sample of the
+    same workload.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the one JSON line; --dump-outputs DIR also
+writes what the last timed step returned as DIR/<name>.npy (inputs and weights are seeded, so two builds run with the
+same arguments can be compared array for array).
 """
 from __future__ import annotations
 
@@ -57,6 +63,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline: the secondary kernels' "
+                         "rooflines, the sustained run, the step breakdown, BASELINE configs 3 / 4 / 5, the chunked "
+                         "run's agreement, host file I/O and the CPU baseline (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (rank 0's batch) as "
+                         "DIR/<name>.npy, float32 / float64")
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU per step")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--words", type=int, default=30)
@@ -533,6 +546,36 @@ def device_census(dev, world):
             "distinct_devices": len({r["pci"] for r in allr})}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, res, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the per-utterance records the last timed step returned (decoder.assemble's, what a caller of
+    the timed path receives), the batch's utterances concatenated in order, one ``<name>.npy`` per field: the DP path
+    (``ph_idx_seq`` / ``ph_time_int``, as float64), the phone and word intervals in seconds ([n, 2] float64), the
+    per-frame ``frame_confidence`` / ``edge_diff`` (float32), the per-utterance ``confidence``, and ``counts``
+    ([B, 4]: DP frames, path length, phones, words -- where one utterance ends and the next begins).  An array whose
+    share of ``limit`` bytes it exceeds is written as a fixed seeded sample of its elements (in order)."""
+    import numpy as np
+    cat = lambda k, dt, tail=(): (np.concatenate([np.asarray(r[k], dt).reshape((-1,) + tail) for r in res])  # noqa: E731
+                                  if res else np.zeros((0,) + tail, dt))
+    arrays = {
+        "ph_idx_seq": cat("ph_idx_seq", np.float64), "ph_time_int": cat("ph_time_int", np.float64),
+        "ph_intervals": cat("ph_intervals", np.float64, (2,)), "word_intervals": cat("word_intervals", np.float64, (2,)),
+        "frame_confidence": cat("frame_confidence", np.float32), "edge_diff": cat("edge_diff", np.float32),
+        "confidence": np.asarray([r["confidence"] for r in res], np.float64),
+        "counts": np.asarray([[r["T"], len(r["ph_idx_seq"]), len(r["ph_seq"]), len(r["word_seq"])] for r in res],
+                             np.float64).reshape(-1, 4),
+    }
+    os.makedirs(path, exist_ok=True)
+    share = limit // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     verdict = check_world(args)
@@ -677,8 +720,10 @@ def main():
     gc.callbacks.remove(gc_cb)
     ops.PROBE = None
     probe.active = True
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     pipe = probe
-    if not args.probe_secondary:       # the secondary kernels' in-pipeline durations: the same loop, untimed
+    if args.full and not args.probe_secondary:   # the secondary kernels' in-pipeline durations: the same loop, untimed
         pipe = ops.KernelProbe("-", extra=SECONDARY)
         ops.PROBE = pipe
         run(min(args.steps, 5))
@@ -767,11 +812,11 @@ def main():
             "sum_intervals_ms": sum(iv), "wall_ms": el * 1e3, "wall_minus_intervals_ms": el * 1e3 - sum(iv),
             "note": "device time between consecutive timed steps' starts; wall_minus_intervals = the last step, its "
                     "drain and the host work around the timed region"}
-    if world == 1 and args.sustained_s > 0 and args.chunk_seconds is None:
+    if args.full and world == 1 and args.sustained_s > 0 and args.chunk_seconds is None:
         n0 = len(host_t)
         out["sustained"] = sustained(run, args.sustained_s, B * args.seconds, out["ms_per_step"])
         del host_t[n0:]
-    c3 = config3_batch(args, world)
+    c3 = config3_batch(args, world) if args.full else 0
     if c3:
         # BASELINE config 3 (512 x 10 s over the node) measured after the weak-scaling region, whose per-GPU batch
         # stays at config 2's 32 so the driver's N = 1..8 curve compares equal per-GPU work
@@ -816,8 +861,9 @@ def main():
         torch.cuda.synchronize()
         return blk
 
-    if (world == 1 and not args.no_extra_configs and args.encoder == "base" and args.seconds == 10.0 and B == 32
-            and args.chunk_seconds is None and not args.serial and args.precision == "split" and not args.host_input):
+    if (args.full and world == 1 and not args.no_extra_configs and args.encoder == "base" and args.seconds == 10.0
+            and B == 32 and args.chunk_seconds is None and not args.serial and args.precision == "split"
+            and not args.host_input):
         # BASELINE configs 4 and 5 on this GPU, driver-observed in the same line (verdict r04 item 4): config 4's
         # per-GPU shard (Hubert-large 24L, 32 x 10 s) and config 5 unchunked (one 300 s utterance, the reference's
         # whole-wave encoding, tools/encoder.py:36-60; its DP held for the next encoder's attention launches)
@@ -831,19 +877,20 @@ def main():
         del t4
         out["config5"] = extra_block("config 5: one 300 s utterance, unchunked (whole-wave encoding), Hubert-base, "
                                      "600 two-phone words (S = 1801), 1 GPU", task, 1, 300.0, 600, 10, 2)
-    if args.chunk_seconds is not None:
+    if args.full and args.chunk_seconds is not None:
         out["chunk_agreement"] = chunk_agreement(task, wav_dev, ph_seqs, word_seqs, p2ws, args.chunk_seconds)
-    if world == 1 and args.chunk_seconds is None and not args.serial:
+    if args.full and world == 1 and args.chunk_seconds is None and not args.serial:
         out["step_breakdown"] = step_breakdown(task, wav_dev, ph_seqs, word_seqs, p2ws, args.steps, el / args.steps)
-    iso = ops.KernelProbe("-", extra=SECONDARY)       # isolated serial steps for the secondary rooflines
-    ops.PROBE = iso
-    for _ in range(2):
+    if args.full:
+        iso = ops.KernelProbe("-", extra=SECONDARY)       # isolated serial steps for the secondary rooflines
+        ops.PROBE = iso
+        for _ in range(2):
+            torch.cuda.synchronize()
+            task.decoder.assemble(task.align_batch(wav_dev, ph_seqs, word_seqs, p2ws, wav_sr=16000, host=False,
+                                                   chunk_seconds=args.chunk_seconds), ph_seqs, word_seqs, p2ws)
         torch.cuda.synchronize()
-        task.decoder.assemble(task.align_batch(wav_dev, ph_seqs, word_seqs, p2ws, wav_sr=16000, host=False,
-                                               chunk_seconds=args.chunk_seconds), ph_seqs, word_seqs, p2ws)
-    torch.cuda.synchronize()
-    ops.PROBE = None
-    out["secondary"] = secondary_rooflines(iso, pipe, n_frames, len(ph_seqs[0]))
+        ops.PROBE = None
+        out["secondary"] = secondary_rooflines(iso, pipe, n_frames, len(ph_seqs[0]))
     ht = host_t[max(args.warmup, 1):max(args.warmup, 1) + args.steps]      # the timed steps
     avg = lambda i: 1e3 * sum(h[i] for h in ht) / max(len(ht), 1)  # noqa: E731
     out["host_cpu"] = {
@@ -856,11 +903,11 @@ def main():
                 "(ctypes launches, allocator, events) and for the previous batch's wait + interval assembly, and "
                 "the whole process's CPU (all threads; per thread over the timed region in threads_cpu_ms_per_step, "
                 "'main' = the launching thread); the GPU step is ms_per_step"}
-    if rank == 0:
+    if args.full and rank == 0:
         import contextlib
         with contextlib.redirect_stdout(sys.stderr):         # the writers' progress prints stay off the JSON line
             out["host_io"] = host_io(wav_np, res, args.seconds)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wav_np, ph_seqs, word_seqs, p2ws, ckpt, args.cpu_sample_s, encoder)
     if rank == 0:
         ht = host_t[-args.steps:]

@@ -219,7 +219,7 @@ def test_bench_two_ranks_config3_block():
     """An N > 1 bench line carries BASELINE config 3 (512 x 10 s over the node) after its weak-scaling region: the
     2-rank rehearsal (gloo, both ranks on GPU 0) times 256 utterances per rank and reports them as `config3`."""
     import json
-    p = _torchrun(["--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "4", "--seconds", "10",
+    p = _torchrun(["--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "4", "--seconds", "10",
                    "--no-cpu-baseline", "--dist-backend", "gloo", "--device", "0"], script="bench.py", timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -242,7 +242,7 @@ def test_bench_eight_ranks_rehearsal():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, "-u", os.path.join(repo, "bench.py"), "--gpus", "8", "--steps", "2",
+    p = subprocess.run([sys.executable, "-u", os.path.join(repo, "bench.py"), "--full", "--gpus", "8", "--steps", "2",
                         "--warmup", "1", "--batch", "2", "--seconds", "10", "--no-cpu-baseline", "--dist-backend",
                         "gloo", "--device", "0"], env=env, cwd=repo, capture_output=True, text=True, timeout=580)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

@@ -502,6 +502,37 @@ def test_bench_config3_batch():
     assert bench.config_name("base", 8, 64) == "config 3 geometry"
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the last step's per-utterance records concatenated in batch order, one float32 /
+    float64 .npy per field, `counts` marking where each utterance's rows end; past its share of the byte limit an
+    array is written as the same seeded sample of its elements on every run."""
+    import bench
+    res = []
+    for b, (T, n) in enumerate(((5, 3), (7, 4))):
+        res.append(dict(T=T, ph_idx_seq=np.arange(n), ph_time_int=np.arange(n) * 2 + b,
+                        frame_confidence=np.full(T, 0.5 + b, np.float32), edge_diff=np.arange(T, dtype=np.float32),
+                        ph_seq=np.array(["a"] * (n - 1)), ph_intervals=np.arange(2.0 * (n - 1)).reshape(-1, 2) + b,
+                        word_seq=np.array(["w"] * b), word_intervals=np.zeros((b, 2)), confidence=0.25 * (b + 1)))
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), res)
+    got = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+    assert sorted(got) == ["confidence", "counts", "edge_diff", "frame_confidence", "ph_idx_seq", "ph_intervals",
+                           "ph_time_int", "word_intervals"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    np.testing.assert_array_equal(got["counts"], [[5, 3, 2, 0], [7, 4, 3, 1]])
+    np.testing.assert_array_equal(got["ph_time_int"], [0, 2, 4, 1, 3, 5, 7])
+    np.testing.assert_array_equal(got["ph_intervals"], np.concatenate([r["ph_intervals"] for r in res]))
+    assert got["word_intervals"].shape == (1, 2) and got["frame_confidence"].dtype == np.float32
+    np.testing.assert_array_equal(got["edge_diff"], np.concatenate([r["edge_diff"] for r in res]))
+    np.testing.assert_array_equal(got["confidence"], [0.25, 0.5])
+    small = [tmp_path / "s1", tmp_path / "s2"]
+    for s in small:
+        bench.dump_outputs(str(s), res, limit=8 * 32)             # 32 bytes per array
+    a, b = (np.load(s / "edge_diff.npy") for s in small)
+    assert a.shape == (8,) and np.array_equal(a, b)
+    assert sum(np.load(small[0] / f).nbytes for f in os.listdir(small[0])) <= 8 * 32
+
+
 def test_bench_gpus_flag_launch_policy():
     """bench.py --gpus N (verdict r04 item 1): without WORLD_SIZE and N > 1 it starts N ranks under
     torch.distributed.run as a child; under a launcher the rank count must equal N; too few visible GPUs (and no
