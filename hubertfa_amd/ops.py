@@ -684,3 +684,31 @@ def resample(x, orig, new, kernel, width, out=None, workspace=None):
               _ptr(workspace), _ptr(out), out.stride(0), _stream(x.device))
     from .resample import target_length
     return out[:, : target_length(N, orig, new)]
+
+
+_lib.register("hfa_logmel_split", [_I_, _I_, _P_, _LL_, _P_, _I_, _I_, _I_, _I_, _I_, _P_, _P_, _F_, _I_, _P_, _LL_,
+                                   _I_, _P_, _P_])
+
+
+def logmel_split(x, basis, fb, *, win_length, hop_length, n_fft, n_mels, clamp, lens=None, out=None, flag=None):
+    """Log-mel spectrogram of the rows of x [B, N] (row stride free, unit element stride) in one fused kernel
+    (hfa_logmel_split); ``basis`` / ``fb`` are the fragment-order split tables melspec.MelSpecExtractor builds
+    (fb [2, 8, nb_pad / 32, 64, 8]).  ``lens``: optional int32 device tensor of per-row lengths.  Returns
+    [B, n_mels, N // hop_length + 1]; out-of-range magnitudes raise ``flag`` (default: the device's split_flag)."""
+    _need(x, torch.float32, "x", contiguous=False)
+    if x.dim() != 2 or x.stride(-1) != 1:
+        raise ValueError("logmel_split: x must be [B, N] with unit element stride")
+    _need(basis, torch.float16, "basis")
+    _need(fb, torch.float16, "fb")
+    B, N = x.shape
+    frames = N // hop_length + 1
+    nb_pad, kpad = fb.shape[2] * 32, (win_length + 127) // 128 * 128
+    if tuple(fb.shape) != (2, 8, nb_pad // 32, 64, 8) or tuple(basis.shape) != (2, nb_pad // 8, kpad // 32, 64, 8):
+        raise ValueError("logmel_split: basis / fb are not the tables of this configuration")   # the kernel trusts them
+    if out is None:
+        out = torch.empty((B, n_mels, frames), dtype=torch.float32, device=x.device)
+    _lib.call("hfa_logmel_split", B, N, _ptr(x), x.stride(0) if B > 1 else 0, _ptr(_lens(lens)), win_length,
+              hop_length, n_fft, n_mels, nb_pad, _ptr(basis), _ptr(fb), float(clamp), frames, _ptr(out),
+              out.stride(0), out.stride(1),
+              _ptr(split_flag(x.device) if flag is None else flag), _stream(x.device))
+    return out

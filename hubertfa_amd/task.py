@@ -68,6 +68,7 @@ class ForcedAlignmentTask:
         self.unitsEncoder = None
         self._upsamplers = {}
         self._chains = {}
+        self._melspec = None
 
     # -- checkpoint ---------------------------------------------------------------------------------------------
     @classmethod
@@ -184,6 +185,52 @@ class ForcedAlignmentTask:
         if chain is None or chain.out_length(min(int(m) for m in lengths) if lengths is not None else n) < 400:
             return None
         return chain
+
+    @property
+    def get_melspec(self):
+        """The log-mel extractor of forced_alignment.py:144-145, built on first use (its tables are device memory the
+        aligner never needs, so on_predict_start does not create it)."""
+        if self._melspec is None:
+            from .melspec import CONFIG_KEYS, MelSpecExtractor
+            self._melspec = MelSpecExtractor(**{k: self.melspec_config.get(k) for k in CONFIG_KEYS},
+                                             device=self.device)
+        return self._melspec
+
+    @torch.no_grad()
+    def make_input_feature(self, waves: torch.Tensor, wav_sr: int | None = None, lengths=None):
+        """binarize.py:273-302 for B waves at once: waves [B, N] (at the melspec rate, or ``wav_sr`` to resample first
+        like load_wav; rows of a variable-length batch zero-padded, ``lengths`` their samples) -> per row
+        (units [1, C, T], melspec [1, n_mels, T], wav_length seconds), each what the row gives alone.  Units are
+        encode_batch's features (the aligner's path); the mel needs the wave at the melspec rate, which the one-pass
+        resampling chain never forms, so for another ``wav_sr`` it is resampled here (task.upsampler)."""
+        sr = self.melspec_config["sample_rate"]
+        waves = waves.to(self.device).float()
+        feats, n_frames, wl = self.encode_batch(waves, wav_sr, lengths)
+        enc = getattr(self.unitsEncoder, "model", None)
+        if getattr(enc, "precision", "f32") == "split" and int(ops.flag_take(ops.split_flag(self.device)).item()):
+            enc.precision = "f32"                 # range guard: a split operand left f16 range, encode on the f32 GEMMs
+            try:
+                feats, n_frames, wl = self.encode_batch(waves, wav_sr, lengths)
+            finally:
+                enc.precision = "split"
+        if lengths is not None and all(int(n) == waves.shape[-1] for n in lengths):
+            lengths = None
+        if wav_sr is not None and wav_sr != sr:
+            waves = self.upsampler(wav_sr)(waves, split=self.unitsEncoder.split_resample).contiguous()
+            if lengths is not None:
+                lengths = [target_length(int(n), wav_sr, sr) for n in lengths]
+                ops.mask_rows(waves, dev_lengths(lengths, waves.device))
+        mel = self.get_melspec.batch(waves, lengths)
+        if self.get_melspec.overflowed():
+            raise ValueError("make_input_feature: a spectral magnitude left f16 range (wave far beyond full scale)")
+        B = waves.shape[0]
+        hop = self.melspec_config["hop_length"]
+        out = []
+        for b in range(B):
+            t = int(n_frames[b]) if isinstance(n_frames, (list, tuple)) else int(n_frames)
+            f = (int(lengths[b]) if lengths is not None else waves.shape[-1]) // hop + 1
+            out.append((feats[b, :t].t().unsqueeze(0), mel[b:b + 1, :, :f], wl[b]))
+        return out
 
     def head_logits(self, feats, n_frames):
         """UNet head (current stream): features -> (logits [B, T, V+2], the head's range-flag snapshot or None)."""

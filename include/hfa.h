@@ -307,6 +307,26 @@ long long hfa_resample_workspace_bytes(int B, int N, int orig, int Kpad);
 int hfa_resample_f32(int B, int N, const float* x, long long x_bs, int orig, int newr, const float* kernel, int Kpad,
                      int width, void* workspace, float* y, long long y_bs, hipStream_t stream);
 
+/* ---- log-mel spectrogram (hubertfa_amd/csrc/melspec.hip) --------------------------------------------------------
+ * Replaces MelSpecExtractor.__call__, tools/get_melspec.py:28-54 (torchaudio MelSpectrogram: zero padding n_fft/2,
+ * STFT center=False, periodic Hann window of win_length centred in n_fft, magnitude, htk mel filterbank norm=None,
+ * log(clamp(., clamp))) as ONE kernel on the split-f16 MFMA (see hfa_conv_gemm_split): x [B, N] f32 (row stride x_bs,
+ * a multiple of 4; split into planes on load) -> y[b, m, f] at y + b*y_bs + m*y_ld + f for m < n_mels, f < frames.
+ * Row b's own length is lens[b] (NULL: N): samples outside [0, lens[b]) read as zeros whatever the buffer holds, frames
+ * f >= lens[b]/hop + 1 are written as zeros.  Tables (hubertfa_amd/melspec.py builds them from the f32 window and the
+ * f32 filterbank, angles in f64), both as split planes in MFMA fragment order, element (lane, j) of a 16-row x 32-deep
+ * block = [row lane & 15][k 8 (lane >> 4) + j]:
+ *   basis [2][nb_pad/8 column blocks][Kpad/32][64][8]: column block 2g + part holds w[k] cos (part 0) / -w[k] sin
+ *         (part 1) (2 pi (k + (n_fft - win_length)/2) bin / n_fft) of the 16 needed bins 16g .. 16g + 15 (first needed
+ *         bin = the first with a non-zero filterbank row), K = win_length padded with zeros to Kpad, a multiple of 128;
+ *   fb    [2][8 mel blocks][nb_pad/32][64][8]: rows mels (zeros past n_mels), k = the needed bins, nb_pad of them.
+ * Envelope (else HFA_EINVAL before any launch): win_length a multiple of 32 and <= 2048, n_fft even and >= win_length,
+ * hop a multiple of 8, n_mels <= 128, nb_pad a multiple of 64, x / basis / fb / y 16-B aligned.  *oflow (may be NULL)
+ * is raised when a magnitude of a valid frame is not finite or >= 65504.  Results do not depend on the frame tile. */
+int hfa_logmel_split(int B, int N, const float* x, long long x_bs, const int32_t* lens, int win_length, int hop,
+                     int n_fft, int n_mels, int nb_pad, const uint16_t* basis, const uint16_t* fb, float clamp,
+                     int frames, float* y, long long y_bs, int y_ld, int* oflow, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
