@@ -259,3 +259,76 @@ class AlignmentDecoder:
         ctc_index = (ctc_index[1:] != ctc_index[:-1]) * ctc != 0
         ctc = ctc[ctc_index]
         return np.array([ph_id for ph_id in ctc if ph_id != 0])
+
+    # -- batched CTC scoring on the GPU (csrc/ctc.hip) ------------------------------------------------------
+    def ctc_targets(self, ph_seq) -> np.ndarray:
+        """The CTC target of a transcript: its phoneme ids with id 0 (SP and the ignored phonemes) dropped
+        (binarize.py:197-198).  KeyError on a phoneme outside the vocabulary."""
+        ids = self.ph_ids(ph_seq).astype(np.int64).reshape(-1)
+        return ids[ids != 0]
+
+    def id_to_phone(self) -> dict:
+        """id -> phoneme name (the first name the vocabulary gives an id; id 0 is "SP")."""
+        inv = {}
+        for ph, i in self.vocab["vocab"].items():
+            inv.setdefault(int(i), ph)
+        inv[0] = "SP"
+        return inv
+
+    def ctc_batch(self, logits, n_frames, ph_seqs, host: bool = True):
+        """Score B transcripts against the head's CTC columns and greedy-decode them, on the GPU.
+
+        logits [B, Tl, V + 2]: the head's logits (column 0 the edge, 1 the CTC blank, 3.. the CTC labels); n_frames:
+        the frame count ``decode`` keeps (:45-50: ``num_frames`` of the row's wav length), an int or one per row,
+        clipped to Tl.  Returns one
+        dict per utterance: ``ctc_nll`` = -log P(transcript | audio) (forced_alignment.py:256-272; inf when the
+        transcript does not fit the frames), ``ctc_confidence`` = clip(exp(-nll / T), 1e-6, 1 - 1e-6) (GHMLoss.py:35-37),
+        ``ctc_phones`` the greedy decode (:145-150) as phoneme names and ``ctc_phone_ids`` as ids.  ``host=False``:
+        the device tensors instead (dict with nll, best, ids, n, T), stream-ordered; ``ctc_results`` completes them."""
+        tgs = [self.ctc_targets(p) for p in ph_seqs]          # (first: an unknown phoneme raises before any GPU work)
+        dev = _device(logits)
+        logits = logits.to(dev).float()
+        if logits.stride(2) != 1:
+            logits = logits.contiguous()
+        B, Tl = logits.shape[:2]
+        if isinstance(n_frames, (list, tuple, np.ndarray)):
+            Ts = [min(int(t), Tl) for t in n_frames]
+        else:
+            Ts = [min(int(n_frames), Tl)] * B
+        if len(Ts) != B or len(ph_seqs) != B:
+            raise ValueError(f"ctc_batch: {B} logit rows, {len(Ts)} frame counts, {len(ph_seqs)} transcripts")
+        nll, best, ids, n = ops.ctc_score(logits, Ts, tgs, [len(t) for t in tgs])
+        dev_out = dict(nll=nll, best=best, ids=ids, n=n, T=Ts)
+        return self.ctc_results(dev_out) if host else dev_out
+
+    def ctc_results(self, dev_out) -> list:
+        """Host half of ctc_batch: the device tensors of ``ctc_batch(host=False)`` -> one dict per utterance."""
+        nll = dev_out["nll"].cpu().numpy()
+        ids, n = dev_out["ids"].cpu().numpy(), dev_out["n"].cpu().numpy()
+        inv = self.id_to_phone()
+        out = []
+        for b, T in enumerate(dev_out["T"]):
+            v = float(nll[b])
+            with np.errstate(over="ignore"):
+                conf = float(np.exp(-v / T)) if T > 0 else (1.0 if v == 0.0 else 0.0)
+            k = ids[b, :int(n[b])].astype(np.int64)
+            out.append(dict(ctc_nll=v, ctc_confidence=float(np.clip(conf, 1e-6, 1 - 1e-6)),
+                            ctc_phones=[inv.get(int(i), str(int(i))) for i in k], ctc_phone_ids=k))
+        return out
+
+
+def ctc_ghm_loss(nll, T, ema):
+    """The reference's ``CTCGHMLoss.forward(valid=True)`` weighting (networks/loss/GHMLoss.py:21-52) of per-utterance
+    CTC losses: each ``nll[b]`` (ops.ctc_score / ``ctc_batch(host=False)["nll"]``, or any tensor-like) is divided by
+    the EMA bin count of its per-frame confidence clip(exp(-nll / T), 1e-6, 1 - 1e-6), and the batch is averaged.
+    ``ema``: the checkpoint's ``CTC_GHM_loss_fn.ema`` buffer (num_bins values); it is not updated (valid=True).
+    Returns a 0-d tensor of nll's dtype on nll's device (0 for an empty batch, as the reference)."""
+    nll = torch.as_tensor(nll)
+    if nll.numel() == 0:
+        return torch.tensor(0.0, device=nll.device)
+    T = torch.as_tensor(T, device=nll.device)
+    ema = torch.as_tensor(ema, device=nll.device).to(nll.dtype)
+    bins = ema.numel()
+    conf = (-nll / T).exp().clamp(1e-6, 1 - 1e-6)
+    idx = torch.floor(conf * bins).long().clamp(0, bins - 1)
+    return (nll / (ema[idx] + 1e-10)).mean()

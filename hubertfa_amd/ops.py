@@ -599,7 +599,7 @@ _lib.register("hfa_set_grid_cap", [_I_])
 
 @contextlib.contextmanager
 def grid_cap(wgs: int):
-    """Launches of the row-streaming kernels (split_f16, LayerNorm, lattice prologue) made by this thread inside the
+    """Launches of the row-streaming kernels (split_f16, LayerNorm, lattice / CTC prologue) made by this thread inside the
     block use at most ``wgs`` workgroups (hfa_set_grid_cap; results identical)."""
     _lib.call("hfa_set_grid_cap", int(wgs))
     try:
@@ -712,3 +712,137 @@ def logmel_split(x, basis, fb, *, win_length, hop_length, n_fft, n_mels, clamp, 
               out.stride(0), out.stride(1),
               _ptr(split_flag(x.device) if flag is None else flag), _stream(x.device))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# CTC head (ctc.hip): gathered log-softmax + argmax, batched sequence likelihood, greedy decode
+# ------------------------------------------------------------------------------------------------------------
+_lib.register("hfa_ctc_max_labels", [])
+_lib.register("hfa_ctc_prologue", [_I_, _I_, _I_, _I_, _P_, _P_, _P_, _LL_, _LL_, _I_, _I_, _P_, _P_, _P_, _P_])
+_lib.register("hfa_ctc_forward", [_I_, _I_, _I_, _P_, _P_, _P_, _P_, _P_, _P_])
+_lib.register("hfa_ctc_greedy", [_I_, _I_, _P_, _P_, _P_, _P_, _P_])
+
+CTC_BLANK_COL, CTC_LABEL_OFF = 1, 2      # the head's layout: [edge, ctc blank, frame class 0, class 1 (= ctc 1), ...]
+CTC_MAX_V = 1024                         # ctc.hip kMaxV
+
+
+def ctc_check_targets(T, targets, L, V):
+    """Host validation of a CTC batch (the kernels trust it): T / L [B] non-negative ints, targets [B, >= max L] with
+    every used id in 1..V-1 (0 is the blank; the binarizer drops it, binarize.py:197-198).  Returns int32 numpy arrays
+    (T [B], L [B], targets [B, Lmax]) with Lmax = max L; unused target slots are zeros."""
+    import numpy as np
+    T = np.asarray(T.cpu() if isinstance(T, torch.Tensor) else T, dtype=np.int64).reshape(-1)
+    L = np.asarray(L.cpu() if isinstance(L, torch.Tensor) else L, dtype=np.int64).reshape(-1)
+    B = T.shape[0]
+    if L.shape[0] != B:
+        raise ValueError(f"ctc: T has {B} rows, L has {L.shape[0]}")
+    if not 0 < int(V) <= CTC_MAX_V:
+        raise ValueError(f"ctc: V = {V} classes is outside 1..{CTC_MAX_V}")
+    if B and (T.min() < 0 or L.min() < 0):
+        raise ValueError("ctc: negative length")
+    Lmax = int(L.max()) if B else 0
+    out = np.zeros((B, Lmax), np.int32)
+    if isinstance(targets, torch.Tensor):
+        targets = targets.cpu().numpy()
+    for b in range(B):
+        row = np.asarray(targets[b], dtype=np.int64).reshape(-1)
+        n = int(L[b])
+        if row.shape[0] < n:
+            raise ValueError(f"ctc: row {b} has {row.shape[0]} targets, L says {n}")
+        row = row[:n]
+        if n and (row.min() < 1 or row.max() >= V):
+            bad = row[(row < 1) | (row >= V)][0]
+            raise ValueError(f"ctc: row {b} has target id {int(bad)} outside 1..{int(V) - 1}")
+        out[b, :n] = row
+    return T.astype(np.int32), L.astype(np.int32), out
+
+
+def _ctc_logits(logits, V, blank_col, label_off):
+    _need(logits, torch.float32, "logits", contiguous=False)
+    if logits.dim() != 3 or logits.stride(2) != 1:
+        raise ValueError("ctc: logits must be [B, T, C] with unit stride in the last dim")
+    C = logits.shape[2]
+    if not 0 < V <= CTC_MAX_V or not 0 <= blank_col < C or label_off < -1 or (V > 1 and V - 1 + label_off >= C):
+        raise ValueError(f"ctc: V = {V}, blank_col = {blank_col}, label_off = {label_off} do not fit {C} columns")
+
+
+def ctc_prologue(logits, T, L, targets, V=None, blank_col=CTC_BLANK_COL, label_off=CTC_LABEL_OFF):
+    """log_softmax over the V CTC classes of every frame, gathered to the transcript, and the argmax class
+    (hfa_ctc_prologue).  logits [B, Tmax, C] f32 (a strided view is fine; class c in column blank_col if c == 0 else
+    c + label_off; V defaults to C - 2, the head's layout), T / L [B] i32, targets [B, Lmax] i32 with ids in 1..V-1
+    (NOT checked here: ctc_check_targets / ctc_score do).  Returns (emis [B, Tmax, Lmax + 1] f32, best [B, Tmax] i32);
+    rows t >= T[b] and columns j > L[b] are left unwritten."""
+    B, Tmax, C = logits.shape
+    V = C - 2 if V is None else int(V)
+    _ctc_logits(logits, V, blank_col, label_off)
+    for t, n in ((T, "T"), (L, "L"), (targets, "targets")):
+        _need(t, torch.int32, n)
+    if T.shape != (B,) or L.shape != (B,) or targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError("ctc_prologue: T / L must be [B] and targets [B, Lmax]")
+    Lmax = targets.shape[1]
+    dev = logits.device
+    emis = torch.empty((B, Tmax, Lmax + 1), dtype=torch.float32, device=dev)
+    best = torch.empty((B, Tmax), dtype=torch.int32, device=dev)
+    _lib.call("hfa_ctc_prologue", B, Tmax, V, Lmax, _ptr(T), _ptr(L), _ptr(logits), logits.stride(1),
+              logits.stride(0), blank_col, label_off, _ptr(targets) if Lmax else None, _ptr(emis), _ptr(best),
+              _stream(dev))
+    return emis, best
+
+
+def ctc_forward(emis, T, L, targets):
+    """-log P(targets | frames) per utterance as f64 [B] (hfa_ctc_forward; +inf for an infeasible pair): emis
+    [B, Tmax, Lmax + 1] from ctc_prologue, T / L [B] i32, targets [B, Lmax] i32."""
+    _need(emis, torch.float32, "emis")
+    for t, n in ((T, "T"), (L, "L"), (targets, "targets")):
+        _need(t, torch.int32, n)
+    B, Tmax, Lp = emis.shape
+    if T.shape != (B,) or L.shape != (B,) or tuple(targets.shape) != (B, Lp - 1):
+        raise ValueError("ctc_forward: T / L must be [B] and targets [B, Lmax] for emis [B, Tmax, Lmax + 1]")
+    nll = torch.empty((B,), dtype=torch.float64, device=emis.device)
+    _lib.call("hfa_ctc_forward", B, Tmax, Lp - 1, _ptr(T), _ptr(L), _ptr(emis) if Tmax else None,
+              _ptr(targets) if Lp > 1 else None, _ptr(nll), _stream(emis.device))
+    return nll
+
+
+def ctc_greedy(best, T):
+    """Greedy CTC collapse of the per-frame argmax (hfa_ctc_greedy; alignment_decoder.py:145-150): best [B, Tmax]
+    i32, T [B] i32 -> (ids [B, Tmax] i32, n [B] i32), row b valid up to n[b]."""
+    _need(best, torch.int32, "best")
+    _need(T, torch.int32, "T")
+    B, Tmax = best.shape
+    if T.shape != (B,):
+        raise ValueError("ctc_greedy: T must be [B]")
+    ids = torch.empty((B, Tmax), dtype=torch.int32, device=best.device)
+    n = torch.empty((B,), dtype=torch.int32, device=best.device)
+    _lib.call("hfa_ctc_greedy", B, Tmax, _ptr(T), _ptr(best) if Tmax else None, _ptr(ids) if Tmax else None, _ptr(n),
+              _stream(best.device))
+    return ids, n
+
+
+def ctc_score(logits, T, targets, L, V=None, blank_col=CTC_BLANK_COL, label_off=CTC_LABEL_OFF):
+    """Score B transcripts against the head's CTC columns: logits [B, Tmax, C] f32 on the GPU (see ctc_prologue), T /
+    L [B] and targets [B, >= max L] as host integers (lists, numpy, CPU tensors; device tensors are copied back to be
+    checked).  The ids are validated on the host (1..V-1, else ValueError, before anything touches the GPU) and reach
+    the device in one pinned non-blocking copy; the workspace comes from torch's allocator.  Returns (nll f64 [B],
+    best i32 [B, Tmax], ids i32 [B, Tmax], n i32 [B]) on the device, stream-ordered."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise TypeError("ctc_score: logits must be a [B, T, C] tensor")
+    Vn = logits.shape[2] - 2 if V is None else int(V)
+    T_h, L_h, tg_h = ctc_check_targets(T, targets, L, Vn)
+    B, Tmax = logits.shape[:2]
+    if T_h.shape[0] != B:
+        raise ValueError(f"ctc_score: {B} logit rows, {T_h.shape[0]} lengths")
+    if B and int(T_h.max()) > Tmax:
+        raise ValueError(f"ctc_score: a row's T = {int(T_h.max())} exceeds the {Tmax} logit frames")
+    _ctc_logits(logits, Vn, blank_col, label_off)
+    Lmax = tg_h.shape[1]
+    if Lmax > int(_lib.lib().hfa_ctc_max_labels()):
+        raise _lib.HFAArgumentError(f"ctc_score: {Lmax} labels exceed the kernel's {_lib.lib().hfa_ctc_max_labels()}",
+                                    _lib.HFA_EINVAL)
+    import numpy as np
+    meta = torch.from_numpy(np.concatenate([T_h, L_h, tg_h.ravel()])).pin_memory().to(logits.device, non_blocking=True)
+    T_t, L_t, tg_t = meta[:B], meta[B:2 * B], meta[2 * B:].view(B, Lmax)
+    emis, best = ctc_prologue(logits, T_t, L_t, tg_t, Vn, blank_col, label_off)
+    nll = ctc_forward(emis, T_t, L_t, tg_t)
+    ids, n = ctc_greedy(best, T_t)
+    return nll, best, ids, n

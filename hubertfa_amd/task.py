@@ -272,31 +272,72 @@ class ForcedAlignmentTask:
         dev_out["redo"] = lambda: self._align_f32(*redo_args)
         return dev_out
 
-    def _align_f32(self, waves, ph_seqs, word_seqs, p2ws, wav_sr, lengths, chunk_seconds):
+    def _f32(self, fn):
+        """Run ``fn`` with the encoder and the head on the f32 GEMMs (the range guard's re-run)."""
         enc = self.unitsEncoder.model
         saved = (getattr(enc, "precision", "f32"), self.head.precision)
         if hasattr(enc, "precision"):
             enc.precision = "f32"
         self.head.precision = "f32"
         try:
-            return self.align_batch(waves, ph_seqs, word_seqs, p2ws, wav_sr=wav_sr, lengths=lengths,
-                                    chunk_seconds=chunk_seconds)
+            return fn()
         finally:
             if hasattr(enc, "precision"):
                 enc.precision = saved[0]
             self.head.precision = saved[1]
 
+    def _align_f32(self, waves, ph_seqs, word_seqs, p2ws, wav_sr, lengths, chunk_seconds, ctc=False):
+        kw = dict(ctc=True) if ctc else {}
+        return self._f32(lambda: self.align_batch(waves, ph_seqs, word_seqs, p2ws, wav_sr=wav_sr, lengths=lengths,
+                                                  chunk_seconds=chunk_seconds, **kw))
+
     def align_batch(self, waves: torch.Tensor, ph_seqs, word_seqs=None, p2ws=None, wav_sr: int | None = None,
-                    host: bool = True, lengths=None, chunk_seconds: float | None = None):
+                    host: bool = True, lengths=None, chunk_seconds: float | None = None, ctc: bool = False):
         """B waveforms [B, N] (at melspec sample_rate, or ``wav_sr`` to resample first, like load_wav) ->
         list of decode results (dicts with ph_seq / ph_intervals / word_seq / word_intervals / confidence / raw
-        path).  Rows of different lengths: zero-pad to N and pass ``lengths``."""
+        path).  Rows of different lengths: zero-pad to N and pass ``lengths``.  ``ctc``: every result also carries
+        ``ctc_nll`` / ``ctc_confidence`` / ``ctc_phones`` (+ ``ctc_phone_ids``; AlignmentDecoder.ctc_batch), scored on
+        the head logits the lattice used (no second head pass; ``host=False``: the device tensors under "ctc")."""
         feats, n_frames, wl = self.encode_batch(waves, wav_sr, lengths, chunk_seconds)
-        dev_out = self.decode_device(feats, n_frames, wl, ph_seqs, word_seqs, p2ws)
-        dev_out = self._guard(dev_out, (waves, ph_seqs, word_seqs, p2ws, wav_sr, lengths, chunk_seconds))
+        if not ctc:
+            dev_out = self.decode_device(feats, n_frames, wl, ph_seqs, word_seqs, p2ws)
+            dev_out = self._guard(dev_out, (waves, ph_seqs, word_seqs, p2ws, wav_sr, lengths, chunk_seconds))
+        else:
+            logits, flag = self.head_logits(feats, n_frames)
+            dev_out = self.lattice_dp(logits, flag, wl, ph_seqs, word_seqs, p2ws)
+            dev_out["ctc"] = self.decoder.ctc_batch(logits, dev_out["T"], ph_seqs, host=False)
+            dev_out = self._guard(dev_out, (waves, ph_seqs, word_seqs, p2ws, wav_sr, lengths, chunk_seconds, True))
         if not host:
             return dev_out
-        return self.decoder.assemble(dev_out, ph_seqs, word_seqs, p2ws)
+        out = self.decoder.assemble(dev_out, ph_seqs, word_seqs, p2ws)
+        if ctc and out and "ctc_nll" not in out[0]:       # (the guard's f32 re-run returns its own CTC values)
+            for r, c in zip(out, self.decoder.ctc_results(dev_out["ctc"])):
+                r.update(c)
+        return out
+
+    @torch.no_grad()
+    def ctc_score_batch(self, waves: torch.Tensor, ph_seqs, wav_sr: int | None = None, lengths=None):
+        """Score B transcripts against their audio with the CTC head, without aligning: waves / ``wav_sr`` /
+        ``lengths`` as align_batch -> one dict per row (AlignmentDecoder.ctc_batch: ctc_nll, ctc_confidence,
+        ctc_phones, ctc_phone_ids) plus ``T``, the row's frames.  Range guard as make_input_feature: the split-f16
+        flags are checked synchronously and a raised one re-runs the batch on the f32 GEMMs."""
+        def run():
+            feats, n_frames, wl = self.encode_batch(waves, wav_sr, lengths)
+            logits, flag = self.head_logits(feats, n_frames)
+            Ts = [self.decoder.num_frames(w, logits.shape[1]) for w in wl]     # the frames decode keeps (= n_frames)
+            dev = self.decoder.ctc_batch(logits, Ts, ph_seqs, host=False)
+            return dev, flag
+        dev, flag = run()
+        enc = getattr(self.unitsEncoder, "model", None)
+        bad = flag is not None and int(flag.item())
+        if getattr(enc, "precision", "f32") == "split":
+            bad = int(ops.flag_take(ops.split_flag(self.device)).item()) or bad
+        if bad:
+            dev, _ = self._f32(run)
+        out = self.decoder.ctc_results(dev)
+        for r, T in zip(out, dev["T"]):
+            r["T"] = T
+        return out
 
     def upload(self, waves) -> torch.Tensor:
         """Host waves (numpy or CPU tensor [B, N]; pinned f32 avoids a staging copy) -> f32 device tensor: a pinned

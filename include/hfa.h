@@ -272,7 +272,7 @@ int hfa_selftest_gelu(long long n, const float* x, float* y, hipStream_t stream)
  * flags[i], then flags[i] = 0, for i < n, stream-ordered (the batch's snapshot travels with its outputs). */
 int hfa_flag_take(int n, int* flags, int* snap, hipStream_t stream);
 /* Workgroup cap (no reference counterpart; 0 = none, the default) for this host thread's later launches of the
- * row-streaming kernels -- hfa_split_f16, hfa_layernorm_f32 / _split, hfa_lattice_prologue: a capped launch runs its
+ * row-streaming kernels -- hfa_split_f16, hfa_layernorm_f32 / _split, hfa_lattice_prologue, hfa_ctc_prologue: a capped launch runs its
  * rows in a grid-stride loop over at most `wgs` workgroups (results identical).  The pipelined step enqueues its side
  * pass (UNet head + lattice, beside the next batch's encoder) under a cap: its tens of thousands of one-row
  * workgroups otherwise cost the encoder more than their work. */
@@ -326,6 +326,38 @@ int hfa_resample_f32(int B, int N, const float* x, long long x_bs, int orig, int
 int hfa_logmel_split(int B, int N, const float* x, long long x_bs, const int32_t* lens, int win_length, int hop,
                      int n_fft, int n_mels, int nb_pad, const uint16_t* basis, const uint16_t* fb, float clamp,
                      int frames, float* y, long long y_bs, int y_ld, int* oflow, hipStream_t stream);
+
+/* ---- CTC head (hubertfa_amd/csrc/ctc.hip) ------------------------------------------------------------------------
+ * The batched sequence likelihood and greedy decode of the head's CTC columns: F.log_softmax + nn.CTCLoss(reduction=
+ * "none") of networks/task/forced_alignment.py:256-272 / networks/loss/GHMLoss.py:12-56, and AlignmentDecoder.ctc,
+ * tools/alignment_decoder.py:145-150.  Utterance b has T[b] frames and L[b] target labels inside [Tmax] / [Lmax]
+ * planes; frames t >= T[b] and targets j >= L[b] are never read into any result, so every utterance gets the bits it
+ * gets alone.  Pointers are aligned to their element size (else HFA_EINVAL before any launch).
+ *
+ * hfa_ctc_prologue (one wave per frame row; honours hfa_set_grid_cap): CTC class c of frame (b,t) is read at
+ * logits[b*bs + t*ld + (c == 0 ? blank_col : c + label_off)] (the head's layout: blank_col = 1, label_off = 2);
+ * V <= 1024 classes.  emis [B,Tmax,Lmax+1] f32: column 0 = log_softmax(blank), column j = log_softmax(targets[b,j-1])
+ * for j <= L[b] (f32 max / log-sum-exp over the V classes); best [B,Tmax] i32 = the argmax class of the raw logits,
+ * the lowest class on ties (np.argmax).  targets [B,Lmax] i32 with ids in 1..V-1: the kernel trusts them, the caller
+ * validates (hubertfa_amd.ops does, on the host).
+ *
+ * hfa_ctc_forward (one workgroup per utterance): nll[b] = -log P(targets[b,:L[b]] | frames < T[b]) as f64, from the
+ * alpha recurrence over the 2L+1 extended states in f32, rebased every 16 steps against an f64 offset (DESIGN.md
+ * §3.5).  An infeasible pair (T[b] < L[b] + adjacent repeats; T[b] = 0 with L[b] > 0) gives +inf, as torch with
+ * zero_infinity=False; L[b] = 0 gives -sum_t emis[t,0]; T[b] = 0 and L[b] = 0 gives 0.  The state range is
+ * register-resident (up to 8 label/blank pairs per lane over 16 waves): Lmax <= hfa_ctc_max_labels() = 8191, beyond
+ * that HFA_EINVAL (no segmented form).
+ *
+ * hfa_ctc_greedy (one workgroup per utterance): ids[b,:n[b]] = best[b,t] for the frames t < T[b], ascending, with
+ * best[b,t] != best[b,t-1] (best[b,-1] = 0) and best[b,t] != 0; ids [B,Tmax] i32, n [B] i32. */
+int hfa_ctc_max_labels(void);
+int hfa_ctc_prologue(int B, int Tmax, int V, int Lmax, const int32_t* T, const int32_t* L, const float* logits,
+                     long long ld, long long bs, int blank_col, int label_off, const int32_t* targets, float* emis,
+                     int32_t* best, hipStream_t stream);
+int hfa_ctc_forward(int B, int Tmax, int Lmax, const int32_t* T, const int32_t* L, const float* emis,
+                    const int32_t* targets, double* nll, hipStream_t stream);
+int hfa_ctc_greedy(int B, int Tmax, const int32_t* T, const int32_t* best, int32_t* ids, int32_t* n,
+                   hipStream_t stream);
 
 #ifdef __cplusplus
 }
