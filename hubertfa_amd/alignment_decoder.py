@@ -275,7 +275,7 @@ class AlignmentDecoder:
         inv[0] = "SP"
         return inv
 
-    def ctc_batch(self, logits, n_frames, ph_seqs, host: bool = True):
+    def ctc_batch(self, logits, n_frames, ph_seqs, host: bool = True, posteriors: bool = False):
         """Score B transcripts against the head's CTC columns and greedy-decode them, on the GPU.
 
         logits [B, Tl, V + 2]: the head's logits (column 0 the edge, 1 the CTC blank, 3.. the CTC labels); n_frames:
@@ -284,7 +284,13 @@ class AlignmentDecoder:
         dict per utterance: ``ctc_nll`` = -log P(transcript | audio) (forced_alignment.py:256-272; inf when the
         transcript does not fit the frames), ``ctc_confidence`` = clip(exp(-nll / T), 1e-6, 1 - 1e-6) (GHMLoss.py:35-37),
         ``ctc_phones`` the greedy decode (:145-150) as phoneme names and ``ctc_phone_ids`` as ids.  ``host=False``:
-        the device tensors instead (dict with nll, best, ids, n, T), stream-ordered; ``ctc_results`` completes them."""
+        the device tensors instead (dict with nll, best, ids, n, T), stream-ordered; ``ctc_results`` completes them.
+
+        ``posteriors``: the CTC forward-backward as well (ops.ctc_posteriors).  Every result also
+        carries, aligned with ``ctc_targets(ph_seq)`` (the transcript's non-SP phones), ``ctc_phone_confidence`` =
+        exp of the posterior-weighted mean log-probability of the phone where the model places it (f64 array; 0 for
+        an infeasible transcript), ``ctc_phone_centre_s`` its expected position in seconds and ``ctc_phone_frames``
+        its expected frame count; ``host=False`` adds occ, frames, centre, logp and L to the device dict."""
         tgs = [self.ctc_targets(p) for p in ph_seqs]          # (first: an unknown phoneme raises before any GPU work)
         dev = _device(logits)
         logits = logits.to(dev).float()
@@ -297,8 +303,14 @@ class AlignmentDecoder:
             Ts = [min(int(n_frames), Tl)] * B
         if len(Ts) != B or len(ph_seqs) != B:
             raise ValueError(f"ctc_batch: {B} logit rows, {len(Ts)} frame counts, {len(ph_seqs)} transcripts")
-        nll, best, ids, n = ops.ctc_score(logits, Ts, tgs, [len(t) for t in tgs])
-        dev_out = dict(nll=nll, best=best, ids=ids, n=n, T=Ts)
+        Ls = [len(t) for t in tgs]
+        if posteriors:
+            nll, occ, frames, centre, logp, best, ids, n = ops.ctc_posteriors(logits, Ts, tgs, Ls)
+            dev_out = dict(nll=nll, best=best, ids=ids, n=n, T=Ts, occ=occ, frames=frames, centre=centre, logp=logp,
+                           L=Ls)
+        else:
+            nll, best, ids, n = ops.ctc_score(logits, Ts, tgs, Ls)
+            dev_out = dict(nll=nll, best=best, ids=ids, n=n, T=Ts)
         return self.ctc_results(dev_out) if host else dev_out
 
     def ctc_results(self, dev_out) -> list:
@@ -314,6 +326,12 @@ class AlignmentDecoder:
             k = ids[b, :int(n[b])].astype(np.int64)
             out.append(dict(ctc_nll=v, ctc_confidence=float(np.clip(conf, 1e-6, 1 - 1e-6)),
                             ctc_phones=[inv.get(int(i), str(int(i))) for i in k], ctc_phone_ids=k))
+        if "logp" in dev_out:
+            frames, centre, logp = (dev_out[k].cpu().numpy().astype(np.float64) for k in ("frames", "centre", "logp"))
+            for b, (r, L) in enumerate(zip(out, dev_out["L"])):
+                r["ctc_phone_confidence"] = np.exp(logp[b, :L])
+                r["ctc_phone_centre_s"] = centre[b, :L] * self.frame_length
+                r["ctc_phone_frames"] = frames[b, :L]
         return out
 
 

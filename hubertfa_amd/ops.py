@@ -846,3 +846,183 @@ def ctc_score(logits, T, targets, L, V=None, blank_col=CTC_BLANK_COL, label_off=
     nll = ctc_forward(emis, T_t, L_t, tg_t)
     ids, n = ctc_greedy(best, T_t)
     return nll, best, ids, n
+
+
+# ---- CTC forward-backward: state posteriors, the per-label report, the loss gradient -----------
+_lib.register("hfa_ctc_forward_alpha", [_I_, _I_, _I_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_])
+_lib.register("hfa_ctc_backward", [_I_, _I_, _I_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_])
+_lib.register("hfa_ctc_grad", [_I_, _I_, _I_, _I_, _P_, _P_, _P_, _LL_, _LL_, _I_, _I_, _P_, _P_, _P_, _P_, _P_, _P_,
+                               _LL_, _LL_, _P_])
+
+
+def _ctc_meta(emis, T, L, targets, who):
+    _need(emis, torch.float32, "emis")
+    for t, n in ((T, "T"), (L, "L"), (targets, "targets")):
+        _need(t, torch.int32, n)
+    B, Tmax, Lp = emis.shape
+    if T.shape != (B,) or L.shape != (B,) or tuple(targets.shape) != (B, Lp - 1):
+        raise ValueError(f"{who}: T / L must be [B] and targets [B, Lmax] for emis [B, Tmax, Lmax + 1]")
+    return B, Tmax, Lp - 1
+
+
+def ctc_forward_alpha(emis, T, L, targets):
+    """ctc_forward that also keeps every step's alpha row (hfa_ctc_forward_alpha): returns (nll f64 [B], the bits
+    ctc_forward gives; alpha [B, Tmax, 2, Lmax + 1] f32, the blank and the label plane, relative to aoff [B, Tmax] f64).
+    Rows t >= T[b] and slots past L[b] are left unwritten."""
+    B, Tmax, Lmax = _ctc_meta(emis, T, L, targets, "ctc_forward_alpha")
+    dev = emis.device
+    nll = torch.empty((B,), dtype=torch.float64, device=dev)
+    alpha = torch.empty((B, Tmax, 2, Lmax + 1), dtype=torch.float32, device=dev)
+    aoff = torch.empty((B, Tmax), dtype=torch.float64, device=dev)
+    _lib.call("hfa_ctc_forward_alpha", B, Tmax, Lmax, _ptr(T), _ptr(L), _ptr(emis) if Tmax else None,
+              _ptr(targets) if Lmax else None, _ptr(nll), _ptr(alpha) if Tmax else None,
+              _ptr(aoff) if Tmax else None, _stream(dev))
+    return nll, alpha, aoff
+
+
+def ctc_backward(emis, T, L, targets, nll, alpha, aoff, out=None):
+    """The beta scan and the state posterior (hfa_ctc_backward) from ctc_forward_alpha's results: returns (occ
+    [B, Tmax, Lmax + 1] f32: column 0 the blanks' summed posterior, column j label j - 1's; frames, centre, logp
+    [B, Lmax] f32: each label's expected frame count, expected position in frames, and posterior-weighted mean
+    log-probability).  Zeros past a row's T / L; an infeasible row gives zeros and logp = -inf.  ``out``: the four
+    tensors to write into."""
+    B, Tmax, Lmax = _ctc_meta(emis, T, L, targets, "ctc_backward")
+    dev = emis.device
+    _need(nll, torch.float64, "nll")
+    _need(alpha, torch.float32, "alpha")
+    _need(aoff, torch.float64, "aoff")
+    if nll.shape != (B,) or tuple(alpha.shape) != (B, Tmax, 2, Lmax + 1) or tuple(aoff.shape) != (B, Tmax):
+        raise ValueError("ctc_backward: nll [B], alpha [B, Tmax, 2, Lmax + 1], aoff [B, Tmax] of ctc_forward_alpha")
+    if out is None:
+        out = (torch.empty((B, Tmax, Lmax + 1), dtype=torch.float32, device=dev),) + tuple(
+            torch.empty((B, Lmax), dtype=torch.float32, device=dev) for _ in range(3))
+    occ, frames, centre, logp = out
+    _need(occ, torch.float32, "occ")
+    if tuple(occ.shape) != (B, Tmax, Lmax + 1):
+        raise ValueError("ctc_backward: occ must be [B, Tmax, Lmax + 1]")
+    for t, n in ((frames, "frames"), (centre, "centre"), (logp, "logp")):
+        _need(t, torch.float32, n)
+        if tuple(t.shape) != (B, Lmax):
+            raise ValueError(f"ctc_backward: {n} must be [B, Lmax]")
+    p = lambda t, on: _ptr(t) if on else None      # noqa: E731
+    _lib.call("hfa_ctc_backward", B, Tmax, Lmax, _ptr(T), _ptr(L), p(emis, Tmax), p(targets, Lmax), _ptr(nll),
+              p(alpha, Tmax), p(aoff, Tmax), p(occ, Tmax), p(frames, Lmax), p(centre, Lmax), p(logp, Lmax),
+              _stream(dev))
+    return occ, frames, centre, logp
+
+
+def ctc_class_index(T, targets, L, V):
+    """The target positions of every row grouped by class, for ctc_grad: validates as ctc_check_targets and returns
+    int32 numpy arrays (T [B], L [B], targets [B, Lmax], cls_ptr [B, V + 1], cls_idx [B, Lmax]): class c's positions
+    in row b are cls_idx[b, cls_ptr[b, c]:cls_ptr[b, c + 1]], ascending (a stable argsort of the row)."""
+    import numpy as np
+    T_h, L_h, tg_h = ctc_check_targets(T, targets, L, V)
+    B, Lmax = tg_h.shape
+    cls_ptr = np.zeros((B, int(V) + 1), np.int32)
+    cls_idx = np.zeros((B, Lmax), np.int32)
+    for b in range(B):
+        n = int(L_h[b])
+        row = tg_h[b, :n]
+        cls_idx[b, :n] = np.argsort(row, kind="stable")
+        cls_ptr[b, 1:] = np.cumsum(np.bincount(row, minlength=int(V))[:int(V)])
+    return T_h, L_h, tg_h, cls_ptr, cls_idx
+
+
+def ctc_grad(logits, T, L, occ, nll, cls_ptr, cls_idx, weight=None, V=None, blank_col=CTC_BLANK_COL,
+             label_off=CTC_LABEL_OFF, out=None):
+    """d (sum_b weight[b] nll[b]) / d logits over the V CTC classes (hfa_ctc_grad): softmax minus the class posterior
+    of ctc_backward's occ, times weight[b] (None: 1), written to the classes' columns of ``out`` (default: zeros of
+    the logits' shape; its other columns are not touched).  Rows t >= T[b] and infeasible rows (nll = +inf) get
+    zeros.  cls_ptr [B, V + 1] / cls_idx [B, Lmax] i32 from ctc_class_index, on the device."""
+    B, Tmax, C = logits.shape
+    V = C - 2 if V is None else int(V)
+    _ctc_logits(logits, V, blank_col, label_off)
+    for t, n in ((T, "T"), (L, "L"), (cls_ptr, "cls_ptr"), (cls_idx, "cls_idx")):
+        _need(t, torch.int32, n)
+    _need(occ, torch.float32, "occ")
+    _need(nll, torch.float64, "nll")
+    Lmax = occ.shape[2] - 1 if occ.dim() == 3 else -1
+    if T.shape != (B,) or L.shape != (B,) or nll.shape != (B,) or tuple(occ.shape) != (B, Tmax, Lmax + 1) or \
+            tuple(cls_ptr.shape) != (B, V + 1) or tuple(cls_idx.shape) != (B, Lmax):
+        raise ValueError("ctc_grad: T / L / nll [B], occ [B, Tmax, Lmax + 1], cls_ptr [B, V + 1], cls_idx [B, Lmax]")
+    if weight is not None:
+        _need(weight, torch.float32, "weight")
+        if weight.shape != (B,):
+            raise ValueError("ctc_grad: weight must be [B]")
+    if out is None:
+        out = torch.zeros((B, Tmax, C), dtype=torch.float32, device=logits.device)
+    _need(out, torch.float32, "grad", contiguous=False)
+    if out.shape != logits.shape or out.stride(2) != 1:
+        raise ValueError("ctc_grad: out must have the logits' shape and unit stride in the last dim")
+    _lib.call("hfa_ctc_grad", B, Tmax, V, Lmax, _ptr(T), _ptr(L), _ptr(logits), logits.stride(1), logits.stride(0),
+              blank_col, label_off, _ptr(occ) if Tmax else None, _ptr(nll), _ptr(cls_ptr),
+              _ptr(cls_idx) if Lmax else None, None if weight is None else _ptr(weight), _ptr(out), out.stride(1),
+              out.stride(0), _stream(logits.device))
+    return out
+
+
+def _ctc_prepare(who, logits, T, targets, L, V, blank_col, label_off):
+    """ctc_score's validation plus the class index; one pinned non-blocking copy of all the integers."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise TypeError(f"{who}: logits must be a [B, T, C] tensor")
+    Vn = logits.shape[2] - 2 if V is None else int(V)
+    T_h, L_h, tg_h, cp_h, ci_h = ctc_class_index(T, targets, L, Vn)
+    B, Tmax = logits.shape[:2]
+    if T_h.shape[0] != B:
+        raise ValueError(f"{who}: {B} logit rows, {T_h.shape[0]} lengths")
+    if B and int(T_h.max()) > Tmax:
+        raise ValueError(f"{who}: a row's T = {int(T_h.max())} exceeds the {Tmax} logit frames")
+    _ctc_logits(logits, Vn, blank_col, label_off)
+    Lmax = tg_h.shape[1]
+    if Lmax > int(_lib.lib().hfa_ctc_max_labels()):
+        raise _lib.HFAArgumentError(f"{who}: {Lmax} labels exceed the kernel's {_lib.lib().hfa_ctc_max_labels()}",
+                                    _lib.HFA_EINVAL)
+    import numpy as np
+    meta = torch.from_numpy(np.concatenate([T_h, L_h, tg_h.ravel(), ci_h.ravel(), cp_h.ravel()]))
+    meta = meta.pin_memory().to(logits.device, non_blocking=True)
+    o = 2 * B + 2 * B * Lmax
+    return (Vn, meta[:B], meta[B:2 * B], meta[2 * B:2 * B + B * Lmax].view(B, Lmax),
+            meta[o:].view(B, Vn + 1), meta[2 * B + B * Lmax:o].view(B, Lmax))
+
+
+def ctc_posteriors(logits, T, targets, L, V=None, blank_col=CTC_BLANK_COL, label_off=CTC_LABEL_OFF):
+    """ctc_score plus the forward-backward report, on one prologue: arguments and validation as ctc_score.  Returns
+    (nll f64 [B], occ f32 [B, Tmax, Lmax + 1], frames, centre, logp f32 [B, Lmax], best, ids, n) on the device: see
+    ctc_backward for occ and the per-label summaries (exp(logp) is the label's confidence) and ctc_score for the
+    rest.  The stored alpha takes B * Tmax * 2 (Lmax + 1) * 4 bytes while this runs."""
+    Vn, T_t, L_t, tg_t, _, _ = _ctc_prepare("ctc_posteriors", logits, T, targets, L, V, blank_col, label_off)
+    emis, best = ctc_prologue(logits, T_t, L_t, tg_t, Vn, blank_col, label_off)
+    nll, alpha, aoff = ctc_forward_alpha(emis, T_t, L_t, tg_t)
+    occ, frames, centre, logp = ctc_backward(emis, T_t, L_t, tg_t, nll, alpha, aoff)
+    ids, n = ctc_greedy(best, T_t)
+    return nll, occ, frames, centre, logp, best, ids, n
+
+
+class _CTCNLL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, T, targets, L, V, blank_col, label_off):
+        x = logits.detach()
+        Vn, T_t, L_t, tg_t, cp_t, ci_t = _ctc_prepare("ctc_nll", x, T, targets, L, V, blank_col, label_off)
+        emis, _ = ctc_prologue(x, T_t, L_t, tg_t, Vn, blank_col, label_off)
+        nll, alpha, aoff = ctc_forward_alpha(emis, T_t, L_t, tg_t)
+        occ = ctc_backward(emis, T_t, L_t, tg_t, nll, alpha, aoff)[0]
+        ctx.save_for_backward(x, T_t, L_t, occ, nll, cp_t, ci_t)
+        ctx.layout = (Vn, blank_col, label_off)
+        return nll.clone()
+
+    @staticmethod
+    def backward(ctx, grad_nll):
+        x, T_t, L_t, occ, nll, cp_t, ci_t = ctx.saved_tensors
+        Vn, blank_col, label_off = ctx.layout
+        g = ctc_grad(x, T_t, L_t, occ, nll, cp_t, ci_t, grad_nll.to(torch.float32).contiguous(), Vn, blank_col,
+                     label_off)
+        return g, None, None, None, None, None, None
+
+
+def ctc_nll(logits, T, targets, L, V=None, blank_col=CTC_BLANK_COL, label_off=CTC_LABEL_OFF):
+    """The CTC loss of forced_alignment.py:256-272 with a gradient: logits [B, Tmax, C] f32 on the GPU in the head's
+    layout (arguments and validation as ctc_score) -> nll f64 [B], differentiable with respect to the logits.  The
+    backward is one hfa_ctc_grad call with weight = grad_output, into zeros of the logits' shape: the columns that
+    are no CTC class get no gradient.  An infeasible row keeps nll = +inf and contributes a zero gradient, which is
+    nn.CTCLoss's zero_infinity for the gradient only."""
+    return _CTCNLL.apply(logits, T, targets, L, V, blank_col, label_off)

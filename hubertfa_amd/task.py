@@ -316,16 +316,20 @@ class ForcedAlignmentTask:
         return out
 
     @torch.no_grad()
-    def ctc_score_batch(self, waves: torch.Tensor, ph_seqs, wav_sr: int | None = None, lengths=None):
+    def ctc_score_batch(self, waves: torch.Tensor, ph_seqs, wav_sr: int | None = None, lengths=None,
+                        posteriors: bool = False):
         """Score B transcripts against their audio with the CTC head, without aligning: waves / ``wav_sr`` /
         ``lengths`` as align_batch -> one dict per row (AlignmentDecoder.ctc_batch: ctc_nll, ctc_confidence,
         ctc_phones, ctc_phone_ids) plus ``T``, the row's frames.  Range guard as make_input_feature: the split-f16
-        flags are checked synchronously and a raised one re-runs the batch on the f32 GEMMs."""
+        flags are checked synchronously and a raised one re-runs the batch on the f32 GEMMs.  ``posteriors``: the
+        per-phone ``ctc_phone_confidence`` / ``ctc_phone_centre_s`` / ``ctc_phone_frames`` as well (ctc_batch)."""
+        kw = dict(posteriors=True) if posteriors else {}
+
         def run():
             feats, n_frames, wl = self.encode_batch(waves, wav_sr, lengths)
             logits, flag = self.head_logits(feats, n_frames)
             Ts = [self.decoder.num_frames(w, logits.shape[1]) for w in wl]     # the frames decode keeps (= n_frames)
-            dev = self.decoder.ctc_batch(logits, Ts, ph_seqs, host=False)
+            dev = self.decoder.ctc_batch(logits, Ts, ph_seqs, host=False, **kw)
             return dev, flag
         dev, flag = run()
         enc = getattr(self.unitsEncoder, "model", None)

@@ -349,7 +349,35 @@ int hfa_logmel_split(int B, int N, const float* x, long long x_bs, const int32_t
  * that HFA_EINVAL (no segmented form).
  *
  * hfa_ctc_greedy (one workgroup per utterance): ids[b,:n[b]] = best[b,t] for the frames t < T[b], ascending, with
- * best[b,t] != best[b,t-1] (best[b,-1] = 0) and best[b,t] != 0; ids [B,Tmax] i32, n [B] i32. */
+ * best[b,t] != best[b,t-1] (best[b,-1] = 0) and best[b,t] != 0; ids [B,Tmax] i32, n [B] i32.
+ *
+ * Forward-backward: the state posterior gamma(t,s) = P(state s at frame t | targets, frames) =
+ * exp(alpha[t,s] + beta[t,s] - y[t,s] + nll), alpha / beta in torch's convention (both include the emission y[t,s]),
+ * and from it the per-label report and the gradient of the loss of forced_alignment.py:256-272 that
+ * nn.CTCLoss's backward gives the reference.  The envelope is hfa_ctc_forward's.
+ *
+ * hfa_ctc_forward_alpha: hfa_ctc_forward (nll has the same bits) that also stores every step's alpha row, relative to
+ * an f64 offset: alpha [B,Tmax,2,Lmax+1] f32, plane 0 = the blank states j <= L[b], plane 1 = the label states
+ * j < L[b]; aoff [B,Tmax] f64 (8-byte aligned); true alpha = alpha + aoff[b,t], -inf = unreachable.  Rows t >= T[b]
+ * and slots past L[b] are not written, except plane 1's slot L[b], which holds garbage.  B*Tmax*2*(Lmax+1)*4 bytes,
+ * the caller's.
+ *
+ * hfa_ctc_backward (one workgroup per utterance): the mirror scan from t = T[b]-1 down, beta in f32 rebased every 16
+ * steps like alpha; gamma = exp(f32(alpha_rel + beta_rel - y) + f32(aoff + boff + nll)).  Writes
+ *   occ [B,Tmax,Lmax+1] f32 (emis's layout): column 0 = sum_j gamma(t, blank_j), column j = gamma(t, label_{j-1}) for
+ *       j <= L[b]; zeros for t >= T[b] and j > L[b];
+ *   frames [B,Lmax] = sum_t occ[t,j+1];  centre = sum_t t occ[t,j+1] / frames (in frames);
+ *   logp = sum_t occ[t,j+1] emis[t,j+1] / frames (the posterior-weighted mean log-probability of label j); zeros for
+ *       j >= L[b].
+ * An infeasible utterance (nll = +inf) gives zeros and logp = -inf (j < L[b]); never NaN.  No atomics: every value has
+ * the bits it has alone at B = 1, whatever form the batch's Lmax selects.
+ *
+ * hfa_ctc_grad (one wave per frame row; honours hfa_set_grid_cap): class c of frame (b,t), read as hfa_ctc_prologue
+ * reads it, gets grad[b*g_bs + t*g_ld + col(c)] = w[b] (softmax(x[b,t])[c] - Gamma[t,c]) = w[b] d nll[b] / d x[b,t,c];
+ * other columns are not touched; rows t >= T[b] and infeasible utterances get zeros.  Gamma of the blank is occ's
+ * column 0; Gamma of class c sums occ's columns of the target positions cls_idx[b, cls_ptr[b,c] .. cls_ptr[b,c+1])
+ * (cls_ptr [B,V+1], cls_idx [B,Lmax] i32: the positions j < L[b] grouped by class, ascending within a class) in that
+ * order, so it is deterministic.  weight [B] f32 or NULL (= 1). */
 int hfa_ctc_max_labels(void);
 int hfa_ctc_prologue(int B, int Tmax, int V, int Lmax, const int32_t* T, const int32_t* L, const float* logits,
                      long long ld, long long bs, int blank_col, int label_off, const int32_t* targets, float* emis,
@@ -358,6 +386,15 @@ int hfa_ctc_forward(int B, int Tmax, int Lmax, const int32_t* T, const int32_t* 
                     const int32_t* targets, double* nll, hipStream_t stream);
 int hfa_ctc_greedy(int B, int Tmax, const int32_t* T, const int32_t* best, int32_t* ids, int32_t* n,
                    hipStream_t stream);
+int hfa_ctc_forward_alpha(int B, int Tmax, int Lmax, const int32_t* T, const int32_t* L, const float* emis,
+                          const int32_t* targets, double* nll, float* alpha, double* aoff, hipStream_t stream);
+int hfa_ctc_backward(int B, int Tmax, int Lmax, const int32_t* T, const int32_t* L, const float* emis,
+                     const int32_t* targets, const double* nll, const float* alpha, const double* aoff, float* occ,
+                     float* frames, float* centre, float* logp, hipStream_t stream);
+int hfa_ctc_grad(int B, int Tmax, int V, int Lmax, const int32_t* T, const int32_t* L, const float* logits,
+                 long long ld, long long bs, int blank_col, int label_off, const float* occ, const double* nll,
+                 const int32_t* cls_ptr, const int32_t* cls_idx, const float* weight, float* grad, long long g_ld,
+                 long long g_bs, hipStream_t stream);
 
 #ifdef __cplusplus
 }

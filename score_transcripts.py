@@ -2,7 +2,7 @@
 networks/task/forced_alignment.py:256-272 and the greedy decode of tools/alignment_decoder.py:145-150), one GPU.
 
     python score_transcripts.py -c model.ckpt -f segments -g Dictionary -d dict.txt [--batch_size 32]
-                                [--hubert_path synth:0]
+                                [--hubert_path synth:0] [--phones]
 
 Pairs every ``*.wav`` under the folder with its ``*.lab`` through the G2P plugins exactly as infer.py does, and writes
 ``<folder>/ctc_scores.csv`` with one row per file: ``name``, ``n_frames``, ``n_phones`` (the transcript's non-SP
@@ -13,6 +13,13 @@ transcript least belongs to their audio come first.  Files are read and batched 
 sample rate, sorted by length, rows zero-padded and processed with per-row lengths), so every file's row equals the
 one it gives alone.  A batch that fails on one input is re-run file by file; a file that fails alone is logged and
 skipped.  No alignment, no multi-GPU.
+
+``--phones`` also writes ``<folder>/ctc_phone_scores.csv`` from the CTC forward-backward (ops.ctc_posteriors), one row
+per (file, non-SP transcript phone): ``name``, ``index`` (among the file's non-SP phones), ``phone``, ``centre_s`` (the
+phone's expected position), ``frames`` (its expected frame count) and ``confidence`` = exp of the posterior-weighted
+mean log-probability of the phone where the model places it: the phone that is wrong stands out as the file's lowest.
+Files come in ``ctc_scores.csv``'s order, phones in transcript order; a file whose transcript does not fit its frames
+gets its rows with confidence 0.  ``ctc_scores.csv`` has the same bytes with and without the flag.
 """
 from __future__ import annotations
 
@@ -44,6 +51,27 @@ def score_row(name, result, ph_seq, vocab) -> dict:
                 phone_edit_distance=edit_distance(result["ctc_phones"], phones))
 
 
+PHONE_COLUMNS = ("name", "index", "phone", "centre_s", "frames", "confidence")
+
+
+def phone_rows(name, result, ph_seq, vocab) -> list:
+    """The ``--phones`` rows of one file from its ctc_score_batch(posteriors=True) result and its transcript."""
+    phones = [p for p in ph_seq if vocab[p] != 0]
+    return [dict(name=name, index=j, phone=p, centre_s=float(result["ctc_phone_centre_s"][j]),
+                 frames=float(result["ctc_phone_frames"][j]), confidence=float(result["ctc_phone_confidence"][j]))
+            for j, p in enumerate(phones)]
+
+
+def write_phone_csv(path, names, rows_by_name) -> None:
+    """Write the phone rows of the files ``names`` in that order (write_csv's), each file's in transcript order."""
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.writer(f)
+        w.writerow(PHONE_COLUMNS)
+        for n in names:
+            for r in rows_by_name[n]:
+                w.writerow([repr(r[c]) if isinstance(r[c], float) else r[c] for c in PHONE_COLUMNS])
+
+
 def write_csv(path, rows) -> list:
     """Write ``rows`` (dicts with COLUMNS) sorted by ctc_confidence ascending (ties by name); returns them sorted.
     Floats are written with repr, so reading them back gives the same values."""
@@ -64,7 +92,8 @@ def write_csv(path, rows) -> list:
               help="(only used when --g2p=='Dictionary') path to the dictionary")
 @click.option("--batch_size", default=32, type=int, help="max files per GPU batch (variable lengths; results equal B=1)")
 @click.option("--hubert_path", default=None, type=str, help="override hubert_config.model_path")
-def main(ckpt, folder, g2p, batch_size, hubert_path, **kwargs):
+@click.option("--phones", is_flag=True, help="also write ctc_phone_scores.csv: one row per non-SP transcript phone")
+def main(ckpt, folder, g2p, batch_size, hubert_path, phones, **kwargs):
     import torch
     import hubertfa_amd.g2p as g2p_mod
     from hubertfa_amd._lib import HFAArgumentError
@@ -95,7 +124,8 @@ def main(ckpt, folder, g2p, batch_size, hubert_path, **kwargs):
                         task.unitsEncoder.encoder_sample_rate)
     recoverable = (HFAArgumentError, ValueError, KeyError, IndexError)   # one input's failure: the GPU stays healthy
     root = pathlib.Path(folder)
-    rows = []
+    rows, by_name = [], {}
+    kw = dict(posteriors=True) if phones else {}
 
     def score(paths, file_sr):
         lens = [items[p][0] for p in paths]
@@ -106,8 +136,12 @@ def main(ckpt, folder, g2p, batch_size, hubert_path, **kwargs):
             if got != lens[r]:
                 raise ValueError(f"{p}: {got} samples read, the header said {lens[r]}")
         res = task.ctc_score_batch(task.upload(wav_h), [items[p][2] for p in paths], wav_sr=file_sr,
-                                   lengths=lens if len(paths) > 1 else None)
-        return [score_row(str(p.relative_to(root).with_suffix("")), r, items[p][2], vocab) for p, r in zip(paths, res)]
+                                   lengths=lens if len(paths) > 1 else None, **kw)
+        names = [str(p.relative_to(root).with_suffix("")) for p in paths]
+        if phones:
+            for n, p, r in zip(names, paths, res):
+                by_name[n] = phone_rows(n, r, items[p][2], vocab)
+        return [score_row(n, r, items[p][2], vocab) for n, p, r in zip(names, paths, res)]
 
     for file_sr, paths in plan:
         try:
@@ -122,7 +156,9 @@ def main(ckpt, folder, g2p, batch_size, hubert_path, **kwargs):
                 except recoverable as e1:
                     errors.append((p, e1))
     out = root / "ctc_scores.csv"
-    write_csv(out, rows)
+    rows = write_csv(out, rows)
+    if phones:
+        write_phone_csv(root / "ctc_phone_scores.csv", [r["name"] for r in rows], by_name)
     for p, e in errors:
         print(f"[error] {p}: {e!r}")
     print(f"{len(rows)} transcript(s) scored -> {out} ({len(errors)} error(s)).")

@@ -1,13 +1,15 @@
 """Time the CTC kernels (csrc/ctc.hip) and align_batch(ctc=True) on the MI355X.
 
     python scripts/ctc_bench.py [--rows 32] [--frames 861] [--phones 45] [--iters 50] [--out FILE] [--no-task]
+                                [--backward]
 
 At config-2 geometry (32 rows x 861 frames, V = 63, about 45 non-SP phones per row) on seeded Gaussian logits in the
 head's layout: HIP-event time of hfa_ctc_prologue, hfa_ctc_forward and hfa_ctc_greedy after warm-up (median and
 minimum over ``--iters`` launches timed one by one, plus one back-to-back window), the Viterbi forward DP on a lattice
 of the same (rows, frames, 2 phones + 1 states) for comparison, and wider transcripts (one row each) through the
 multi-wave forms.  Then, on the synthetic Hubert-base task, the wall difference align_batch(ctc=True) - align_batch()
-for 32 x 10 s waves.  Needs a GPU: there is no CPU path.
+for 32 x 10 s waves.  ``--backward`` adds the forward-backward kernels at the same shapes: hfa_ctc_forward_alpha (beside
+the plain forward it must not slow down), hfa_ctc_backward and hfa_ctc_grad.  Needs a GPU: there is no CPU path.
 """
 from __future__ import annotations
 
@@ -66,6 +68,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-task", action="store_true")
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ctc_bench: no GPU (timings come from the MI355X only)")
@@ -89,6 +92,21 @@ def main():
         fwd = event_times(lambda: ops.ctc_forward(emis, T_t, L_t, tg), iters)
         gre = event_times(lambda: ops.ctc_greedy(best, T_t), iters)
         return pro, fwd, gre
+
+    def fb_kernels(B, T, L, iters):
+        logits = (torch.randn(B, T, V + 2, generator=torch.Generator().manual_seed(3)) * 3).cuda()
+        tg_h = np.random.default_rng(12).integers(1, V, (B, L))
+        _, _, _, cp, ci = ops.ctc_class_index([T] * B, tg_h, [L] * B, V)
+        T_t, L_t, tg, cp, ci = i32([T] * B), i32([L] * B), i32(tg_h), i32(cp), i32(ci)
+        emis, _ = ops.ctc_prologue(logits, T_t, L_t, tg)
+        nll, alpha, aoff = ops.ctc_forward_alpha(emis, T_t, L_t, tg)
+        out = ops.ctc_backward(emis, T_t, L_t, tg, nll, alpha, aoff)
+        grad = torch.zeros_like(logits)
+        fwd = event_times(lambda: ops.ctc_forward(emis, T_t, L_t, tg), iters)
+        fwa = event_times(lambda: ops.ctc_forward_alpha(emis, T_t, L_t, tg), iters)
+        bwd = event_times(lambda: ops.ctc_backward(emis, T_t, L_t, tg, nll, alpha, aoff, out=out), iters)
+        grd = event_times(lambda: ops.ctc_grad(logits, T_t, L_t, out[0], nll, cp, ci, out=grad), iters)
+        return fwd, fwa, bwd, grd
 
     pro, fwd, gre = kernels(B, T, L, args.iters)
     say(f"ctc {B} x {T} frames, V = {V}, {L} labels ({2 * L + 1} states), one wave per utterance:")
@@ -114,6 +132,17 @@ def main():
     for Lw, Tw in ((300, 3000), (1000, 3000), (4000, 9000), (8191, 9000)):
         _, f, _ = kernels(1, Tw, Lw, max(5, args.iters // 5))
         say(f"ctc forward 1 x {Tw} frames, {Lw} labels: median {f[0] * 1e3:.0f} us ({f[0] * 1e3 / Tw:.3f} us per step)")
+
+    if args.backward:
+        shapes = [(B, T, L, args.iters)] + [(1, Tw, Lw, max(5, args.iters // 5))
+                                            for Lw, Tw in ((300, 3000), (1000, 3000), (4000, 9000), (8191, 9000))]
+        for Bb, Tb, Lb, it in shapes:
+            fwd, fwa, bwd, grd = fb_kernels(Bb, Tb, Lb, it)
+            say(f"ctc forward-backward {Bb} x {Tb} frames, {Lb} labels (median us, us per step): "
+                f"forward {fwd[0] * 1e3:.0f} ({fwd[0] * 1e3 / Tb:.3f}), "
+                f"forward_alpha {fwa[0] * 1e3:.0f} ({fwa[0] * 1e3 / Tb:.3f}, {fwa[0] / fwd[0]:.2f} x), "
+                f"backward {bwd[0] * 1e3:.0f} ({bwd[0] * 1e3 / Tb:.3f}, {bwd[0] / fwd[0]:.2f} x), "
+                f"grad {grd[0] * 1e3:.0f}")
 
     if not args.no_task:
         from hubertfa_amd import synth
