@@ -1026,3 +1026,225 @@ def ctc_nll(logits, T, targets, L, V=None, blank_col=CTC_BLANK_COL, label_off=CT
     are no CTC class get no gradient.  An infeasible row keeps nll = +inf and contributes a zero gradient, which is
     nn.CTCLoss's zero_infinity for the gradient only."""
     return _CTCNLL.apply(logits, T, targets, L, V, blank_col, label_off)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Full-label alignment losses (loss.hip): the four full-label terms of the reference's _get_loss, their gradient
+# with respect to the head logits and the counts behind the GHM tables (DESIGN.md §3.7)
+# ------------------------------------------------------------------------------------------------------------
+_lib.register("hfa_fa_frame_loss", [_I_, _I_, _I_, _I_, ctypes.c_double, _P_, _P_, _P_, _LL_, _LL_, _P_, _P_, _P_, _P_, _P_, _P_,
+                                    _P_, _P_, _P_, _LL_, _LL_, _P_])
+_lib.register("hfa_fa_emd", [_I_, _I_, _P_, _P_, _P_, _LL_, _LL_, _P_, _P_, _P_, _P_])
+_lib.register("hfa_fa_loss_reduce", [_I_, _I_, _I_, _I_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_, _P_])
+
+FA_LOSS_NAMES = ("ph_frame_GHM_loss", "ph_edge_GHM_loss", "ph_edge_EMD_loss", "ph_edge_diff_loss")
+FA_MAX_BINS = 64                         # loss.hip kMaxBins
+
+
+def fa_table_slices(V: int, num_bins: int) -> dict:
+    """Where the reference's six GHM buffers sit in the packed ``tables`` / ``hist`` array of the loss kernels."""
+    V, nb = int(V), int(num_bins)
+    o = [0, V, V + nb, V + 2 * nb, V + 2 * nb + 3, V + 3 * nb + 3, V + 3 * nb + 6]
+    names = ("ph_frame_GHM_loss_fn.class_ema", "ph_frame_GHM_loss_fn.GD_ema", "ph_edge_GHM_loss_fn.GD_stat_ema",
+             "ph_edge_GHM_loss_fn.label_stat_ema_each_class", "ph_edge_diff_GHM_loss_fn.GD_stat_ema",
+             "ph_edge_diff_GHM_loss_fn.label_stat_ema_each_class")
+    return {n: slice(o[i], o[i + 1]) for i, n in enumerate(names)}
+
+
+def _fa_i32(x, device, name):
+    if not isinstance(x, torch.Tensor):
+        import numpy as np
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    if x.device.type != "cuda":
+        x = x.to(device)
+    if x.dtype != torch.int32:
+        if x.dtype.is_floating_point:
+            raise TypeError(f"{name}: expected an integer (or bool) tensor, got {x.dtype}")
+        x = x.to(torch.int32)
+    return x.contiguous()
+
+
+def _fa_check(who, logits, T, label_type, ph_frame=None, ph_edge=None, ph_mask=None):
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise TypeError(f"{who}: logits must be a [B, T, V + 2] tensor")
+    _need(logits, torch.float32, f"{who}: logits", contiguous=False)
+    B, Tmax, C = logits.shape
+    V = C - 2
+    if logits.stride(2) != 1 and C > 1:
+        raise ValueError(f"{who}: logits need unit stride in the last dim")
+    if V < 1 or V > CTC_MAX_V:
+        raise ValueError(f"{who}: V = {V} frame classes is outside 1..{CTC_MAX_V}")
+    for t, n in ((T, "T"), (label_type, "label_type")):
+        _need(t, torch.int32, f"{who}: {n}")
+        if t.shape != (B,):
+            raise ValueError(f"{who}: {n} must be [B]")
+    if ph_frame is not None:
+        _need(ph_frame, torch.int32, f"{who}: ph_frame")
+        if tuple(ph_frame.shape) != (B, Tmax):
+            raise ValueError(f"{who}: ph_frame must be [B, Tmax]")
+    if ph_edge is not None:
+        _need(ph_edge, torch.float32, f"{who}: ph_edge")
+        if tuple(ph_edge.shape) != (B, Tmax):
+            raise ValueError(f"{who}: ph_edge must be [B, Tmax]")
+    if ph_mask is not None:
+        _need(ph_mask, torch.int32, f"{who}: ph_mask")
+        if tuple(ph_mask.shape) != (B, V):
+            raise ValueError(f"{who}: ph_mask must be [B, V]")
+    return B, Tmax, V
+
+
+def fa_frame_loss(logits, T, label_type, ph_frame, ph_edge, ph_mask, tables, num_bins, label_smoothing=0.0,
+                  coef=None, emd_fac=None, grad=None, terms=None, bins=None):
+    """The frame, edge and edge-difference terms of every frame (hfa_fa_frame_loss): logits [B, Tmax, V + 2] f32 (a
+    strided view is fine), T / label_type [B] i32, ph_frame [B, Tmax] i32, ph_edge [B, Tmax] f32, ph_mask [B, V] i32,
+    tables f32 [V + 3 num_bins + 6] (fa_table_slices), all on the device.  Returns (terms [B, Tmax, 3] f32, bins
+    [B, Tmax, 5] i32); with ``coef`` ([4] f32 on the device: upstream / normaliser per loss, in FA_LOSS_NAMES' order)
+    also the gradient, written to column 0 and columns 2.. of ``grad`` (default: zeros of the logits' shape), the EMD's
+    share included when ``emd_fac`` (fa_emd) is given."""
+    B, Tmax, V = _fa_check("fa_frame_loss", logits, T, label_type, ph_frame, ph_edge, ph_mask)
+    nb = int(num_bins)
+    _need(tables, torch.float32, "fa_frame_loss: tables")
+    if tables.shape != (V + 3 * nb + 6,):
+        raise ValueError(f"fa_frame_loss: tables must be [{V + 3 * nb + 6}] for V = {V}, num_bins = {nb}")
+    dev = logits.device
+    if terms is None:
+        terms = torch.empty((B, Tmax, 3), dtype=torch.float32, device=dev)
+    if bins is None:
+        bins = torch.empty((B, Tmax, 5), dtype=torch.int32, device=dev)
+    _need(terms, torch.float32, "fa_frame_loss: terms")
+    _need(bins, torch.int32, "fa_frame_loss: bins")
+    if tuple(terms.shape) != (B, Tmax, 3) or tuple(bins.shape) != (B, Tmax, 5):
+        raise ValueError("fa_frame_loss: terms must be [B, Tmax, 3] and bins [B, Tmax, 5]")
+    g_ld = g_bs = 0
+    if coef is not None:
+        _need(coef, torch.float32, "fa_frame_loss: coef")
+        if coef.shape != (4,):
+            raise ValueError("fa_frame_loss: coef must be [4]")
+        if grad is None:
+            grad = torch.zeros(logits.shape, dtype=torch.float32, device=dev)
+        _need(grad, torch.float32, "fa_frame_loss: grad", contiguous=False)
+        if grad.shape != logits.shape or grad.stride(2) != 1:
+            raise ValueError("fa_frame_loss: grad must have the logits' shape and unit stride in the last dim")
+        g_ld, g_bs = grad.stride(1), grad.stride(0)
+        if emd_fac is not None:
+            _need(emd_fac, torch.int32, "fa_frame_loss: emd_fac")
+            if tuple(emd_fac.shape) != (B, Tmax):
+                raise ValueError("fa_frame_loss: emd_fac must be [B, Tmax]")
+    elif grad is not None or emd_fac is not None:
+        raise ValueError("fa_frame_loss: grad / emd_fac need coef")
+    _lib.call("hfa_fa_frame_loss", B, Tmax, V, nb, float(label_smoothing), _ptr(T), _ptr(label_type), _ptr(logits),
+              logits.stride(1), logits.stride(0), _ptr(ph_frame), _ptr(ph_edge), _ptr(ph_mask), _ptr(tables),
+              _ptr(terms), _ptr(bins), _ptr(coef), _ptr(emd_fac), _ptr(grad), g_ld, g_bs, _stream(dev))
+    return (terms, bins) if coef is None else (terms, bins, grad)
+
+
+def fa_emd(logits, T, label_type, ph_edge):
+    """The EMD term's scans (hfa_fa_emd) over the edge column of logits [B, Tmax, V + 2]: returns (sums [B, 3] f64 =
+    sum |forward cumsum| and sum |reverse cumsum| over the row's own frames and |sum d|, what each padding column adds
+    to the first; fac [B, Tmax] i32 = the gradient's sign
+    counts per frame)."""
+    B, Tmax, _ = _fa_check("fa_emd", logits, T, label_type, None, ph_edge)
+    sums = torch.empty((B, 3), dtype=torch.float64, device=logits.device)
+    fac = torch.empty((B, Tmax), dtype=torch.int32, device=logits.device)
+    _lib.call("hfa_fa_emd", B, Tmax, _ptr(T), _ptr(label_type), _ptr(logits), logits.stride(1), logits.stride(0),
+              _ptr(ph_edge), _ptr(sums), _ptr(fac) if Tmax else None, _stream(logits.device))
+    return sums, fac
+
+
+def fa_loss_reduce(T, label_type, terms, bins, ph_frame, emd_sums, V, num_bins):
+    """Sums, normalisers and counts (hfa_fa_loss_reduce) of fa_frame_loss's and fa_emd's results: returns (row_terms
+    [B, 4] f64 unnormalised, losses [4] f64, norm [4] f64, hist i32 [V + 3 num_bins + 6] in tables' layout)."""
+    _need(terms, torch.float32, "fa_loss_reduce: terms")
+    _need(bins, torch.int32, "fa_loss_reduce: bins")
+    _need(ph_frame, torch.int32, "fa_loss_reduce: ph_frame")
+    _need(emd_sums, torch.float64, "fa_loss_reduce: emd_sums")
+    _need(T, torch.int32, "fa_loss_reduce: T")
+    _need(label_type, torch.int32, "fa_loss_reduce: label_type")
+    if terms.dim() != 3 or terms.shape[2] != 3:
+        raise ValueError("fa_loss_reduce: terms must be [B, Tmax, 3]")
+    B, Tmax = terms.shape[:2]
+    if tuple(bins.shape) != (B, Tmax, 5) or tuple(ph_frame.shape) != (B, Tmax) or tuple(emd_sums.shape) != (B, 3) or \
+            T.shape != (B,) or label_type.shape != (B,):
+        raise ValueError("fa_loss_reduce: bins [B, Tmax, 5], ph_frame [B, Tmax], emd_sums [B, 3], T / label_type [B]")
+    V, nb = int(V), int(num_bins)
+    dev = terms.device
+    row_terms = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    out = torch.empty(8, dtype=torch.float64, device=dev)
+    hist = torch.empty(V + 3 * nb + 6, dtype=torch.int32, device=dev)
+    _lib.call("hfa_fa_loss_reduce", B, Tmax, V, nb, _ptr(T), _ptr(label_type), _ptr(terms), _ptr(bins),
+              _ptr(ph_frame), _ptr(emd_sums), _ptr(row_terms), _ptr(out), _P(out.data_ptr() + 32), _ptr(hist),
+              _stream(dev))
+    return row_terms, out[:4], out[4:], hist
+
+
+_FA_HALF_EMD = (1.0, 1.0, 0.5, 1.0)
+_FA_HALF = {}                            # the same on each device, made once
+
+
+class _FALoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, T, label_type, ph_frame, ph_edge, ph_mask, tables, num_bins, label_smoothing):
+        x = logits.detach()
+        V = x.shape[2] - 2
+        sums, fac = fa_emd(x, T, label_type, ph_edge)
+        terms, bins = fa_frame_loss(x, T, label_type, ph_frame, ph_edge, ph_mask, tables, num_bins, label_smoothing)
+        row_terms, losses, norm, hist = fa_loss_reduce(T, label_type, terms, bins, ph_frame, sums, V, num_bins)
+        # upstream -> coef without a host synchronisation: 1 / normaliser (1/2 of it for the EMD), 0 where none
+        half = _FA_HALF.get(x.device)
+        if half is None:
+            half = _FA_HALF[x.device] = torch.tensor(_FA_HALF_EMD, dtype=torch.float64, device=x.device)
+        inv = torch.where(norm > 0, half / norm.clamp_min(1.0), torch.zeros_like(norm))
+        ctx.save_for_backward(x, T, label_type, ph_frame, ph_edge, ph_mask, tables, fac, inv, terms, bins)
+        ctx.cfg = (int(num_bins), float(label_smoothing))
+        ctx.mark_non_differentiable(row_terms, norm, hist, sums)
+        return losses.clone(), row_terms, norm, hist, sums
+
+    @staticmethod
+    def backward(ctx, g_losses, _g_rows, _g_norm, _g_hist, _g_sums):
+        x, T, label_type, ph_frame, ph_edge, ph_mask, tables, fac, inv, terms, bins = ctx.saved_tensors
+        nb, ls = ctx.cfg
+        coef = (g_losses.to(torch.float64) * inv).to(torch.float32)
+        grad = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        grad[:, :, 1] = 0                                    # the kernel writes every other column of every frame
+        g = fa_frame_loss(x, T, label_type, ph_frame, ph_edge, ph_mask, tables, nb, ls, coef=coef, emd_fac=fac,
+                          grad=grad, terms=terms, bins=bins)[2]
+        return g, None, None, None, None, None, None, None, None
+
+
+def fa_loss(logits, T, label_type, ph_frame, ph_edge, ph_mask, tables, num_bins=10, label_smoothing=0.0,
+            stats=False, check=True):
+    """The four full-label losses of the reference's _get_loss (forced_alignment.py:188-254) over the rows with
+    label_type >= 2, in FA_LOSS_NAMES' order, as an f64 [4] device tensor that is differentiable with respect to the
+    logits: logits [B, Tmax, V + 2] f32 on the GPU in the head's layout (a strided view is fine; Tmax is the view's, as
+    the reference's EMD mean runs over it), T / label_type [B], ph_frame [B, Tmax] integer, ph_edge [B, Tmax] f32,
+    ph_mask [B, V] integer or bool, tables f32 [V + 3 num_bins + 6] (fa_table_slices; constants for the gradient).
+    The backward is one hfa_fa_frame_loss launch with device-resident coefficients: a gradient of the logits' shape,
+    zeros in column 1 and wherever a row or frame does not take part.  ``stats``: also (row_terms [B, 4] f64
+    unnormalised, norm [4] f64, hist i32 in tables' layout, fa_emd's sums [B, 3]).  ``check`` (one host synchronisation): T within the view
+    and the taking-part frames' ph_frame within 0..V-1."""
+    if not isinstance(logits, torch.Tensor) or logits.device.type != "cuda":
+        raise _lib.HFALibraryError("fa_loss: logits must be a GPU tensor (no CPU fallback)")
+    dev = logits.device
+    T = _fa_i32(T, dev, "T")
+    label_type = _fa_i32(label_type, dev, "label_type")
+    ph_frame = _fa_i32(ph_frame, dev, "ph_frame")
+    ph_mask = _fa_i32(ph_mask, dev, "ph_mask")
+    if not isinstance(ph_edge, torch.Tensor):
+        import numpy as np
+        ph_edge = torch.from_numpy(np.ascontiguousarray(np.asarray(ph_edge, dtype=np.float32)))
+    ph_edge = ph_edge.to(dev, torch.float32).contiguous()
+    tables = tables.detach().to(dev, torch.float32).contiguous()
+    B, Tmax, V = _fa_check("fa_loss", logits, T, label_type, ph_frame, ph_edge, ph_mask)
+    if not 0 < int(num_bins) <= FA_MAX_BINS:
+        raise ValueError(f"fa_loss: num_bins = {num_bins} is outside 1..{FA_MAX_BINS}")
+    if check and B and Tmax:
+        part = (torch.arange(Tmax, device=dev)[None, :] < T[:, None]) & (label_type[:, None] >= 2)
+        bad = torch.stack([(T > Tmax).any() | (T < 0).any(), (((ph_frame < 0) | (ph_frame >= V)) & part).any()])
+        bad = bad.tolist()
+        if bad[0]:
+            raise ValueError(f"fa_loss: a row's T is outside 0..{Tmax}")
+        if bad[1]:
+            raise ValueError(f"fa_loss: a ph_frame id is outside 0..{V - 1}")
+    out = _FALoss.apply(logits, T, label_type, ph_frame, ph_edge, ph_mask, tables, int(num_bins),
+                        float(label_smoothing))
+    return out if stats else out[0]

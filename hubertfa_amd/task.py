@@ -2,8 +2,9 @@
 
 Kept: ``load_from_checkpoint(path)`` (reads ``state_dict`` + ``hyper_parameters`` of a Lightning .ckpt),
 ``forward(x[B,T,C]) -> (ph_frame_logits, ph_edge_logits, ctc_logits)`` (:284-292), ``on_predict_start`` (:143-152),
-``predict_step(batch, batch_idx)`` (:154-186) with the same 7-tuple result.  Training/validation/losses are out
-of scope; loss-module buffers in the checkpoint are ignored.
+``predict_step(batch, batch_idx)`` (:154-186) with the same 7-tuple result.  Training and validation steps are out
+of scope; the aligner ignores the loss-module buffers in the checkpoint (``loss_batch`` evaluates _get_loss's five
+losses on labelled items: hubertfa_amd/losses.py).
 
 Added: ``align_batch`` — B equal-length utterances through one pass of GPU kernels (resample, Hubert, gather,
 UNet+head, lattice prologue, DP, backtrack), the path the benchmark and the batched CLI use.
@@ -69,6 +70,7 @@ class ForcedAlignmentTask:
         self._upsamplers = {}
         self._chains = {}
         self._melspec = None
+        self._fa_loss = None
 
     # -- checkpoint ---------------------------------------------------------------------------------------------
     @classmethod
@@ -342,6 +344,72 @@ class ForcedAlignmentTask:
         for r, T in zip(out, dev["T"]):
             r["T"] = T
         return out
+
+    @property
+    def fa_loss(self):
+        """The reference's loss object (_get_loss, forced_alignment.py:188-282) on the device kernels, built on first
+        use from the checkpoint's loss_config (absent: the reference's defaults); its tables start at ones unless the
+        caller loads a checkpoint's buffers (losses.FALoss.from_checkpoint)."""
+        if self._fa_loss is None:
+            from .losses import FALoss
+            cfg = self.hparams.get("loss_config") or {}
+            V = self.vocab["vocab_size"]
+            self._fa_loss = FALoss.from_checkpoint({}, cfg, vocab_size=V, device=self.device) \
+                if cfg.get("function") else FALoss(V, device=self.device)
+        return self._fa_loss
+
+    @torch.no_grad()
+    def loss_batch(self, waves: torch.Tensor, items, wav_sr: int | None = None, lengths=None):
+        """How well the model explains B labelled items: waves / ``wav_sr`` / ``lengths`` as align_batch; ``items``: per
+        row a dict with ``ph_seq`` (phone names) and ``ph_dur`` (seconds; empty or absent: a weak label), as
+        labels.read_transcriptions gives them.  One encoder and head pass, the targets of labels.make_ph_data at each
+        row's frame count, and FALoss(valid=True).  Returns {"losses": the batch's five losses in _get_loss's order
+        (numpy f64), "rows": per row a dict of the four full-label losses over the row's own normalisers (its frames;
+        its frame pairs for the difference term; NaN for a weak row), ``ctc_nll`` and ``frames``} -- a row's values are
+        those it gives alone.  Range guard as ctc_score_batch."""
+        from .labels import make_ph_data
+
+        def run():
+            feats, n_frames, wl = self.encode_batch(waves, wav_sr, lengths)
+            logits, flag = self.head_logits(feats, n_frames)
+            return logits, [self.decoder.num_frames(w, logits.shape[1]) for w in wl], flag
+        logits, Ts, flag = run()
+        enc = getattr(self.unitsEncoder, "model", None)
+        bad = flag is not None and int(flag.item())
+        if getattr(enc, "precision", "f32") == "split":
+            bad = int(ops.flag_take(ops.split_flag(self.device)).item()) or bad
+        if bad:
+            logits, Ts, _ = self._f32(run)
+        B, V = len(Ts), self.vocab["vocab_size"]
+        if len(items) != B:
+            raise ValueError(f"loss_batch: {B} waves, {len(items)} items")
+        Tmax = max(Ts)
+        frame_length = self.melspec_config["hop_length"] / self.melspec_config["sample_rate"]
+        ph_frame, ph_edge = np.zeros((B, Tmax), np.int32), np.zeros((B, Tmax), np.float32)
+        ph_mask, seqs, types = np.zeros((B, V), np.int32), [], []
+        for b, it in enumerate(items):
+            durs = list(it.get("ph_dur") or [])
+            lt = 2 if durs else 1
+            ids = [self.vocab["vocab"][p] for p in it["ph_seq"]]
+            seq, edge, frame, mask, _ = make_ph_data(self.vocab, Ts[b], lt, ids, durs, frame_length)
+            if seq is None:
+                raise ValueError(f"loss_batch: item {it.get('name', b)} has no phone but SP")
+            ph_frame[b, :Ts[b]], ph_edge[b, :Ts[b]], ph_mask[b] = frame, edge, mask
+            seqs.append(seq)
+            types.append(lt)
+        losses, st = self.fa_loss(logits[:, :Tmax], Ts, ph_frame, ph_edge, seqs, [len(s) for s in seqs], ph_mask,
+                                  types, valid=True, stats=True)
+        row_terms, sums, nll = (st[k].cpu().numpy() for k in ("row_terms", "emd_sums", "ctc_nll"))
+        rows = []
+        for b in range(B):
+            T = Ts[b]
+            full = types[b] >= 2
+            own = [row_terms[b, 0] / T, row_terms[b, 1] / T, (sums[b, 0] + sums[b, 1]) * 0.5 / T,
+                   row_terms[b, 3] / (T - 1) if T > 1 else 0.0] if full and T > 0 else [float("nan")] * 4
+            r = {n: float(v) for n, v in zip(ops.FA_LOSS_NAMES, own)}
+            r.update(ctc_nll=float(nll[b]), frames=int(T))
+            rows.append(r)
+        return {"losses": np.asarray([float(v) for v in losses]), "rows": rows}
 
     def upload(self, waves) -> torch.Tensor:
         """Host waves (numpy or CPU tensor [B, N]; pinned f32 avoids a staging copy) -> f32 device tensor: a pinned

@@ -272,7 +272,8 @@ int hfa_selftest_gelu(long long n, const float* x, float* y, hipStream_t stream)
  * flags[i], then flags[i] = 0, for i < n, stream-ordered (the batch's snapshot travels with its outputs). */
 int hfa_flag_take(int n, int* flags, int* snap, hipStream_t stream);
 /* Workgroup cap (no reference counterpart; 0 = none, the default) for this host thread's later launches of the
- * row-streaming kernels -- hfa_split_f16, hfa_layernorm_f32 / _split, hfa_lattice_prologue, hfa_ctc_prologue: a capped launch runs its
+ * row-streaming kernels -- hfa_split_f16, hfa_layernorm_f32 / _split, hfa_lattice_prologue, hfa_ctc_prologue,
+ * hfa_ctc_grad, hfa_fa_frame_loss, hfa_fa_loss_reduce: a capped launch runs its
  * rows in a grid-stride loop over at most `wgs` workgroups (results identical).  The pipelined step enqueues its side
  * pass (UNet head + lattice, beside the next batch's encoder) under a cap: its tens of thousands of one-row
  * workgroups otherwise cost the encoder more than their work. */
@@ -395,6 +396,50 @@ int hfa_ctc_grad(int B, int Tmax, int V, int Lmax, const int32_t* T, const int32
                  long long ld, long long bs, int blank_col, int label_off, const float* occ, const double* nll,
                  const int32_t* cls_ptr, const int32_t* cls_idx, const float* weight, float* grad, long long g_ld,
                  long long g_bs, hipStream_t stream);
+
+/* ---- full-label alignment losses (hubertfa_amd/csrc/loss.hip) ------------------------------------------------------
+ * The four full-label terms of _get_loss, networks/task/forced_alignment.py:188-254, fused, with their gradient with
+ * respect to the head logits and the counts the reference's EMA tables are updated from:
+ * ph_frame_GHM_loss (GHMLoss, networks/loss/GHMLoss.py:221-302), ph_edge_GHM_loss and ph_edge_diff_loss
+ * (MultiLabelGHMLoss(1), GHMLoss.py:117-211, the latter on forced_alignment.py:224-236's pairs) and ph_edge_EMD_loss
+ * (networks/loss/BinaryEMDLoss.py:4-15).  Conventions of the CTC block.  logits: the head's [B,Tmax,V+2] rows, frame
+ * (b,t) at logits + b*bs + t*ld, column 0 the edge, column 1 never read or written, columns 2.. the V <= 1024 frame
+ * classes.  Row b takes part iff label_type[b] >= 2, its frames t < T[b]; nothing else in any buffer (NaN included),
+ * and no logit of a class with ph_mask[b,c] == 0, reaches any output.  ph_frame [B,Tmax] i32 (class ids; clamped to
+ * 0..V-1, the caller validates), ph_edge [B,Tmax] f32 in [0,1], ph_mask [B,V] i32 (non-zero = live).
+ * tables, f32 [V + 3 num_bins + 6] (num_bins <= 64), is the reference's six buffers in one array, and hist (i32) the
+ * matching counts: class_ema [V] | GD_ema [num_bins] (ph_frame_GHM_loss_fn) | GD_stat_ema [num_bins] |
+ * label_stat_ema_each_class [3] (ph_edge_GHM_loss_fn) | the same two of ph_edge_diff_GHM_loss_fn.
+ * Loss order everywhere: 0 frame, 1 edge, 2 EMD, 3 edge difference.
+ *
+ * hfa_fa_frame_loss (one wave per frame row; honours hfa_set_grid_cap; label_smoothing is a double so that the frame
+ * targets are f32(ls) and f32(1 - ls), the reference's float one-hot clamped by Python floats): terms [B,Tmax,3] f32 = the weighted frame,
+ * edge and edge-difference (pair t, t+1; t + 1 < T[b]) loss of frame t, zeros where not taking part; bins [B,Tmax,5]
+ * i32 = frame GD bin, edge GD bin, edge label bin, difference GD bin, difference label bin, -1 where not counted.
+ * grad (may be NULL; frame (b,t) at grad + b*g_bs + t*g_ld): column 0 and columns 2..V+1 receive
+ * coef[0] d frame + coef[1] d edge + coef[3] d difference (+ coef[2] sigmoid'(x) emd_fac[b,t] with emd_fac, from
+ * hfa_fa_emd) of the SUMS of the terms, zeros where not taking part; coef [4] f32 on the device = upstream gradient /
+ * normaliser per loss (x 1/2 for the EMD), so a backward pass needs no host synchronisation.
+ *
+ * hfa_fa_emd (one workgroup per row): forward and reverse inclusive scans of d_t = sigmoid(x_t) - ph_edge_t over
+ * t < T[b] in f64.  sums [B,3] f64 = sum_{u<T} |F_u|, sum_u |R_u| and |sum d| (each of the Tmax - T[b] padding columns
+ * adds the last to the first, which hfa_fa_loss_reduce does in closed form; for u >= T[b] R_u is 0); fac [B,Tmax] i32 = sum_{u>=t} sign(F_u) + sum_{u<=t} sign(R_u), padding included (exact
+ * integer counts), zeros where not taking part.
+ *
+ * hfa_fa_loss_reduce (one workgroup per row over a fixed tree on the frame index, then the rows in ascending order;
+ * honours hfa_set_grid_cap): row_terms [B,4] f64 = each row's unnormalised sums (EMD: (sums[b,0] + (Tmax - T[b]) sums[b,2] + sums[b,1]) / 2),
+ * the same bits alone and in a batch; hist as above (integer atomics); norm [4] f64 = live frames, frames, full rows x
+ * Tmax, pairs; losses [4] f64 = sum_b row_terms / norm (0 where norm is 0). */
+int hfa_fa_frame_loss(int B, int Tmax, int V, int num_bins, double label_smoothing, const int32_t* T,
+                      const int32_t* label_type, const float* logits, long long ld, long long bs,
+                      const int32_t* ph_frame, const float* ph_edge, const int32_t* ph_mask, const float* tables,
+                      float* terms, int32_t* bins, const float* coef, const int32_t* emd_fac, float* grad,
+                      long long g_ld, long long g_bs, hipStream_t stream);
+int hfa_fa_emd(int B, int Tmax, const int32_t* T, const int32_t* label_type, const float* logits, long long ld,
+               long long bs, const float* ph_edge, double* sums, int32_t* fac, hipStream_t stream);
+int hfa_fa_loss_reduce(int B, int Tmax, int V, int num_bins, const int32_t* T, const int32_t* label_type,
+                       const float* terms, const int32_t* bins, const int32_t* ph_frame, const double* emd_sums,
+                       double* row_terms, double* losses, double* norm, int32_t* hist, hipStream_t stream);
 
 #ifdef __cplusplus
 }
