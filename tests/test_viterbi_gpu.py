@@ -228,6 +228,51 @@ def test_forward_many_states_vs_oracle(T, S, force_k, pitch8):
     np.testing.assert_allclose(fc[0].cpu().numpy(), f_ref, rtol=2e-6, atol=0, equal_nan=True)
 
 
+@pytest.mark.parametrize("T,S,pitch8", [(40, 1, False), (40, 2, False), (50, 3, False), (90, 5, True),
+                                        (200, 16, False), (200, 17, False), (300, 30, False), (600, 128, False),
+                                        (600, 129, False), (5, 12, False)])
+def test_forward_narrow_states_vs_oracle(T, S, pitch8):
+    """The narrow forms, each as its own B = 1 launch so Smax is the narrow value itself: the backtrack's LDS row
+    pitches of 16 (Smax <= 16) and 32 (Smax 17..30) bytes, whole rows up to 128 states and the 64-column band past
+    them, one- and two-state lattices, a state pitch of 8, and more states than frames (the reference takes it: every
+    path is -inf and the confidences are NaN, compared as equal).  Bit-exact dp, bt, curr, path and times with the
+    pinned C oracle, frame_confidence at rtol 2e-6."""
+    from hubertfa_amd import ops
+    from oracle import decode as od
+    r = np.random.default_rng(T * 7 + S)
+    V = 63
+    ids = r.integers(1, V, S).astype(np.int64)
+    ids[::3] = 0
+    ids[0] = ids[-1] = 0
+    logits = (3 * r.standard_normal((T, V))).astype(np.float32)
+    ph_prob_log = torch.log_softmax(torch.from_numpy(logits), -1).numpy()
+    edge = np.clip(r.uniform(-0.2, 1.2, T), 0, 1)
+    pl, E, nE, cu, dp, bt, pad = od.lattice_inputs(ids, ph_prob_log, edge)
+    d_ref, b_ref, c_ref = od.forward_pass(T, S, pl, nE, E, cu.copy(), dp.copy(), bt.copy(), ids, pad)
+    P = -(-S // 8) * 8 if pitch8 else S
+
+    def padded(a, fill):
+        out = np.full(a.shape[:-1] + (P,), fill, dtype=a.dtype)
+        out[..., :S] = a
+        return out
+    dev = torch.device("cuda")
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))[None].to(dev)
+    dp_t, cu_t = t(padded(dp, -np.inf)), t(padded(cu, -np.inf))
+    bt_t = torch.full((1, T, P), -1, dtype=torch.int8, device=dev)
+    ids_t = t(padded(ids.astype(np.int32), 0))
+    Tt = torch.tensor([T], dtype=torch.int32, device=dev)
+    St = torch.tensor([S], dtype=torch.int32, device=dev)
+    ops.viterbi_forward(t(padded(pl, 0.0)), t(nE), t(E), cu_t, dp_t, bt_t, ids_t, Tt, St)
+    assert np.array_equal(dp_t[0, :, :S].cpu().numpy().view(np.int32), d_ref.view(np.int32))
+    assert np.array_equal(bt_t[0, 1:, :S].cpu().numpy().astype(np.int32), b_ref[1:])
+    assert np.array_equal(cu_t[0, :S].cpu().numpy().view(np.int64), c_ref.view(np.int64))
+    idx, tint, n, fc = ops.viterbi_backtrack(dp_t, bt_t, ids_t, Tt, St)
+    i_ref, t_ref, f_ref = od.backtrack(d_ref, b_ref, ids)
+    k = int(n[0])
+    assert np.array_equal(idx[0, :k].cpu().numpy(), i_ref) and np.array_equal(tint[0, :k].cpu().numpy(), t_ref)
+    np.testing.assert_allclose(fc[0].cpu().numpy(), f_ref, rtol=2e-6, atol=0, equal_nan=True)
+
+
 def test_reference_api_forward_pass_and_decode():
     from hubertfa_amd.alignment_decoder import AlignmentDecoder
     z, n = _cases()
