@@ -4,7 +4,8 @@ The four full-label terms run as ops.fa_loss (csrc/loss.hip), the weak-label ter
 as CTCGHMLoss.forward (networks/loss/GHMLoss.py:21-56); all five are differentiable with respect to the head logits.  The
 seven EMA tables live on the device under the reference's buffer names and are updated, when ``valid`` is False, by
 update_ema (GHMLoss.py:5-9) from the kernels' integer counts; the loss always uses the tables as they were before.
-Ramp-up schedulers (forced_alignment.py:70-79) are not built: ``total`` applies the plain weights.
+``total`` applies the plain weights; the ramp-up schedulers (forced_alignment.py:70-79) are hubertfa_amd/schedulers.py's,
+applied by train.HeadTrainer.
 """
 from __future__ import annotations
 
@@ -66,12 +67,14 @@ class FALoss:
         return torch.cat([self.tables[n] for n in self._slices])
 
     # -- the losses ---------------------------------------------------------------------------------------------
-    def __call__(self, logits, T, ph_frame, ph_edge, ph_id_seq, L, ph_mask, label_type, valid=False, stats=False):
+    def __call__(self, logits, T, ph_frame, ph_edge, ph_id_seq, L, ph_mask, label_type, valid=False, stats=False, check=True):
         """The five losses in _get_loss's order (a list of 0-d f64 device tensors): logits [B, Tmax, V + 2] on the GPU;
         T, L, label_type [B] host integers (lists, numpy or CPU tensors); ph_frame / ph_edge [B, Tmax], ph_mask [B, V];
         ph_id_seq: the rows' target id lists (or a padded [B, Lmax] array with L).  ``valid`` False: the tables are
         updated after the losses are formed.  ``stats``: also a dict with row_terms [B, 4] (unnormalised), norm [4],
-        ctc_nll [B] (NaN where the row has no weak label), hist, emd_sums [B, 3] (ops.fa_emd)."""
+        ctc_nll [B] (NaN where the row has no weak label), hist, emd_sums [B, 3] (ops.fa_emd).  ``check`` False: skip
+        ops.fa_loss's validation of T and ph_frame, which waits for the device (a caller that validated its targets once,
+        as train.HeadTrainer does when it caches them)."""
         import numpy as np
         dev = logits.device
         T_h = np.asarray(torch.as_tensor(T).cpu() if isinstance(T, torch.Tensor) else T, dtype=np.int64).reshape(-1)
@@ -81,7 +84,7 @@ class FALoss:
         B = logits.shape[0]
         losses4, row_terms, norm, hist, emd_sums = ops.fa_loss(
             logits, T_h.astype(np.int32), lt_h.astype(np.int32), ph_frame, ph_edge, ph_mask, self.packed_tables(),
-            self.num_bins, self.label_smoothing, stats=True)
+            self.num_bins, self.label_smoothing, stats=True, check=check)
         # the weak-label term: CTCGHMLoss.forward (GHMLoss.py:21-56) over the rows with label_type >= 1
         weak = np.nonzero(lt_h >= 1)[0]
         ctc = torch.zeros((), dtype=torch.float64, device=dev)

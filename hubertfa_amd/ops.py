@@ -1248,3 +1248,134 @@ def fa_loss(logits, T, label_type, ph_frame, ph_edge, ph_mask, tables, num_bins=
     out = _FALoss.apply(logits, T, label_type, ph_frame, ph_edge, ph_mask, tables, int(num_bins),
                         float(label_smoothing))
     return out if stats else out[0]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# Head fine-tuning (train.hip): the Linear weight gradient and the clipped AdamW step
+# ------------------------------------------------------------------------------------------------------------
+_D_ = ctypes.c_double
+_lib.register("hfa_wgrad_workspace_bytes", [_I_, _I_, _I_, _I_], ctypes.c_longlong)
+_lib.register("hfa_wgrad_chunk_rows", [])
+_lib.register("hfa_wgrad_f32", [_I_, _I_, _I_, _I_, _P_, _LL_, _LL_, _P_, _LL_, _LL_, _P_, _P_, _LL_, _P_, _P_, _P_, _P_])
+_lib.register("hfa_adamw_f32", [_LL_, _P_, _P_, _P_, _P_, _P_, _D_, _D_, _D_, _D_, _D_, _D_, _D_, _D_, _P_, _P_])
+
+
+def wgrad_workspace(B, Tmax, N, C, device) -> torch.Tensor:
+    """The workspace hfa_wgrad_f32 needs for these sizes (uint8, 8-byte aligned as every torch allocation is)."""
+    n = _lib.lib().hfa_wgrad_workspace_bytes(int(B), int(Tmax), int(N), int(C))
+    if n < 0:
+        _lib.check(int(n), "hfa_wgrad_workspace_bytes")
+    return torch.empty(max(int(n), 8), dtype=torch.uint8, device=device)
+
+
+def wgrad(G, X, lens, dW=None, db=None, sumsq=None, workspace=None):
+    """The weight gradient of y = x W^T + b over a variable-length batch (hfa_wgrad_f32): G [B, Tmax, N] f32 = d loss /
+    d y and X [B, Tmax, C] f32 (strided views with unit stride in the last dim are fine), lens [B] i32 on the device; rows
+    t >= lens[b] never reach a result.  Returns (dW [N, C] f32, db [N] f32, sumsq 0-d f64 = sum dW^2 + sum db^2), written
+    into ``dW`` (a row-strided view is fine) / ``db`` / ``sumsq`` where given.  C % 8 == 0.  Deterministic: the same bits
+    on every run and under grid_cap."""
+    for t, n in ((G, "G"), (X, "X")):
+        _need(t, torch.float32, f"wgrad: {n}", contiguous=False)
+        if t.dim() != 3 or (t.stride(2) != 1 and t.shape[2] > 1):
+            raise ValueError(f"wgrad: {n} must be [B, Tmax, width] with unit stride in the last dim")
+    B, Tmax, N = G.shape
+    C = X.shape[2]
+    if tuple(X.shape[:2]) != (B, Tmax):
+        raise ValueError("wgrad: G and X must share [B, Tmax]")
+    if N < 1 or C < 8 or C % 8:
+        raise ValueError(f"wgrad: N = {N} must be >= 1 and C = {C} a positive multiple of 8")
+    _need(lens, torch.int32, "wgrad: lens")
+    if lens.shape != (B,):
+        raise ValueError("wgrad: lens must be [B]")
+    dev = G.device
+    if dW is None:
+        dW = torch.empty((N, C), dtype=torch.float32, device=dev)
+    if db is None:
+        db = torch.empty(N, dtype=torch.float32, device=dev)
+    if sumsq is None:
+        sumsq = torch.empty((), dtype=torch.float64, device=dev)
+    _need(dW, torch.float32, "wgrad: dW", contiguous=False)
+    _need(db, torch.float32, "wgrad: db")
+    _need(sumsq, torch.float64, "wgrad: sumsq")
+    if tuple(dW.shape) != (N, C) or dW.stride(1) != 1 or (N > 1 and dW.stride(0) < C) or db.shape != (N,) or \
+            sumsq.numel() != 1:
+        raise ValueError("wgrad: dW must be [N, C] (rows at least C apart), db [N], sumsq one f64")
+    if workspace is None:
+        workspace = wgrad_workspace(B, Tmax, N, C, dev)
+    _need(workspace, torch.uint8, "wgrad: workspace")
+    if workspace.numel() < _lib.lib().hfa_wgrad_workspace_bytes(B, Tmax, N, C):
+        raise ValueError("wgrad: workspace too small (wgrad_workspace)")
+    # (a size-1 dim's stride is arbitrary in torch: pass the width instead)
+    ldg = G.stride(1) if Tmax > 1 else max(N, G.stride(1))
+    ldx = X.stride(1) if Tmax > 1 else max(C, X.stride(1))
+    _lib.call("hfa_wgrad_f32", B, Tmax, N, C, _ptr(G), ldg, G.stride(0) if B > 1 else 0, _ptr(X), ldx,
+              X.stride(0) if B > 1 else 0, _ptr(lens), _ptr(dW), dW.stride(0) if N > 1 else C, _ptr(db), _ptr(sumsq),
+              _ptr(workspace), _stream(dev))
+    return dW, db, sumsq
+
+
+def adamw_step(p, m, v, g, sumsq, skipped, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, step=None,
+               bc1=None, bc2=None, max_norm=0.0):
+    """clip_grad_norm_(max_norm) + one torch.optim.AdamW step over flat f32 buffers, in place (hfa_adamw_f32): p, m
+    (exp_avg), v (exp_avg_sq), g [n]; sumsq the 0-d f64 device scalar wgrad wrote (the gradient's squared norm);
+    ``skipped`` i32 [1] on the device, incremented instead of stepping when sumsq is not finite.  ``step`` (1-based)
+    gives the bias corrections 1 - beta^step unless ``bc1`` / ``bc2`` are passed; max_norm <= 0: no clipping.  Nothing
+    here waits for the device."""
+    for t, n in ((p, "p"), (m, "m"), (v, "v"), (g, "g")):
+        _need(t, torch.float32, f"adamw_step: {n}")
+        if t.dim() != 1 or t.numel() != p.numel():
+            raise ValueError(f"adamw_step: {n} must be a flat buffer of p's size")
+    _need(sumsq, torch.float64, "adamw_step: sumsq")
+    _need(skipped, torch.int32, "adamw_step: skipped")
+    if sumsq.numel() != 1 or skipped.numel() != 1:
+        raise ValueError("adamw_step: sumsq and skipped hold one element each")
+    if bc1 is None or bc2 is None:
+        if step is None or int(step) < 1:
+            raise ValueError("adamw_step: step (>= 1) or bc1 and bc2")
+        bc1 = 1.0 - float(beta1) ** int(step) if bc1 is None else bc1
+        bc2 = 1.0 - float(beta2) ** int(step) if bc2 is None else bc2
+    _lib.call("hfa_adamw_f32", p.numel(), _ptr(p), _ptr(m), _ptr(v), _ptr(g), _ptr(sumsq), float(max_norm), float(lr),
+              float(beta1), float(beta2), float(eps), float(weight_decay), float(bc1), float(bc2), _ptr(skipped),
+              _stream(p.device))
+
+
+class _HeadLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, ys, W, Ws, b, lens, flag, grad_out):
+        if Ws is not None:
+            out = linear_split(ys if ys is not None else split(y, flag=flag), Ws, b, flag=flag)
+        else:
+            out = linear(y, W, b)
+        ctx.save_for_backward(y, lens)
+        ctx.grad_out = grad_out
+        ctx.wshape = tuple(W.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, lens = ctx.saved_tensors
+        N, C = ctx.wshape
+        dW, db, sumsq = ctx.grad_out if ctx.grad_out is not None else (None, None, None)
+        if g.stride(-1) != 1:
+            g = g.contiguous()
+        dW, db, _ = wgrad(g, y, lens, dW, db, sumsq)
+        return None, None, dW, None, db, None, None, None
+
+
+def head_linear(y, ys, Wp, Ws, bp, lens, flag=None, grad_out=None):
+    """The head's nn.Linear (forced_alignment.py:53-55) as LatticeHead.logits runs it, differentiable with respect to its
+    weight and bias only (the backbone is frozen: no gradient to ``y``): y [B, T, C] f32 and, on the split path, its
+    planes ``ys`` (None: split here) with the padded weight's planes ``Ws`` -- linear_split; Ws None: ops.linear on the
+    f32 weight.  Wp [n, C], bp [n]; returns logits [B, T, n] (the caller slices the padded columns off).  Backward is one
+    ops.wgrad over the rows t < lens[b] (lens [B] i32 on the device); ``grad_out`` = (dW [n, C], db [n], sumsq): write
+    the gradient there (the trainer's flat buffer) instead of into new tensors."""
+    _need(y, torch.float32, "head_linear: y", contiguous=False)
+    _need(Wp, torch.float32, "head_linear: Wp")
+    _need(bp, torch.float32, "head_linear: bp")
+    _need(lens, torch.int32, "head_linear: lens")
+    if y.dim() != 3 or Wp.dim() != 2 or Wp.shape[1] != y.shape[2] or bp.shape != (Wp.shape[0],) or \
+            lens.shape != (y.shape[0],):
+        raise ValueError("head_linear: y [B, T, C], Wp [n, C], bp [n], lens [B]")
+    if Ws is not None and tuple(Ws.shape) != (2, *Wp.shape):
+        raise ValueError("head_linear: Ws must be Wp's split planes [2, n, C]")
+    return _HeadLinear.apply(y, ys, Wp, Ws, bp, lens, flag, grad_out)

@@ -2,8 +2,8 @@
 
 Kept: ``load_from_checkpoint(path)`` (reads ``state_dict`` + ``hyper_parameters`` of a Lightning .ckpt),
 ``forward(x[B,T,C]) -> (ph_frame_logits, ph_edge_logits, ctc_logits)`` (:284-292), ``on_predict_start`` (:143-152),
-``predict_step(batch, batch_idx)`` (:154-186) with the same 7-tuple result.  Training and validation steps are out
-of scope; the aligner ignores the loss-module buffers in the checkpoint (``loss_batch`` evaluates _get_loss's five
+``predict_step(batch, batch_idx)`` (:154-186) with the same 7-tuple result.  Training is limited to the head on a frozen
+backbone (hubertfa_amd/train.py); validation steps are out of scope; the aligner ignores the loss-module buffers in the checkpoint (``loss_batch`` evaluates _get_loss's five
 losses on labelled items: hubertfa_amd/losses.py).
 
 Added: ``align_batch`` — B equal-length utterances through one pass of GPU kernels (resample, Hubert, gather,
@@ -71,6 +71,7 @@ class ForcedAlignmentTask:
         self._chains = {}
         self._melspec = None
         self._fa_loss = None
+        self.checkpoint_path = None
 
     # -- checkpoint ---------------------------------------------------------------------------------------------
     @classmethod
@@ -79,9 +80,11 @@ class ForcedAlignmentTask:
         hp = dict(ckpt["hyper_parameters"])
         if hubert_model_path is not None:
             hp["hubert_config"] = dict(hp["hubert_config"], model_path=hubert_model_path)
-        return cls(hp["vocab_text"], hp.get("vowel_text"), hp["model_config"], hp["hubert_config"],
+        self = cls(hp["vocab_text"], hp.get("vowel_text"), hp["model_config"], hp["hubert_config"],
                    hp["melspec_config"], hp.get("optimizer_config"), hp.get("loss_config"),
                    state_dict=ckpt["state_dict"], device=device)
+        self.checkpoint_path = checkpoint_path     # (train.HeadTrainer re-reads the file for what the aligner drops)
+        return self
 
     # -- reference surface --------------------------------------------------------------------------------------
     def on_predict_start(self):

@@ -273,7 +273,7 @@ int hfa_selftest_gelu(long long n, const float* x, float* y, hipStream_t stream)
 int hfa_flag_take(int n, int* flags, int* snap, hipStream_t stream);
 /* Workgroup cap (no reference counterpart; 0 = none, the default) for this host thread's later launches of the
  * row-streaming kernels -- hfa_split_f16, hfa_layernorm_f32 / _split, hfa_lattice_prologue, hfa_ctc_prologue,
- * hfa_ctc_grad, hfa_fa_frame_loss, hfa_fa_loss_reduce: a capped launch runs its
+ * hfa_ctc_grad, hfa_fa_frame_loss, hfa_fa_loss_reduce, hfa_wgrad_f32: a capped launch runs its
  * rows in a grid-stride loop over at most `wgs` workgroups (results identical).  The pipelined step enqueues its side
  * pass (UNet head + lattice, beside the next batch's encoder) under a cap: its tens of thousands of one-row
  * workgroups otherwise cost the encoder more than their work. */
@@ -440,6 +440,44 @@ int hfa_fa_emd(int B, int Tmax, const int32_t* T, const int32_t* label_type, con
 int hfa_fa_loss_reduce(int B, int Tmax, int V, int num_bins, const int32_t* T, const int32_t* label_type,
                        const float* terms, const int32_t* bins, const int32_t* ph_frame, const double* emd_sums,
                        double* row_terms, double* losses, double* norm, int32_t* hist, hipStream_t stream);
+
+/* ---- head fine-tuning (hubertfa_amd/csrc/train.hip) ------------------------------------------------------------------
+ * What a training step of the head alone needs after the losses' d loss / d logits: the backbone frozen
+ * as optimizer_config.freeze allows (networks/task/forced_alignment.py:499-501) under a new or continued nn.Linear head
+ * (load_pretrained, forced_alignment.py:118-125).  Conventions of the CTC block.
+ *
+ * hfa_wgrad_f32 replaces autograd's backward of the head's nn.Linear (forced_alignment.py:53-55) with respect to its
+ * weight and bias, over a variable-length batch:
+ *   dW[n*ldw + c] = sum_b sum_{t < lens[b]} G[b,t,n] X[b,t,c],  db[n] = sum_b sum_{t < lens[b]} G[b,t,n]  (n < N, c < C),
+ *   *sumsq (f64) = sum dW^2 + sum db^2 of the f32 values written (torch.nn.utils.clip_grad_norm_'s total norm, squared).
+ * G row (b,t) at G + b*g_bs + t*ldg (N floats, ldg >= N), X row (b,t) at X + b*x_bs + t*ldx (C floats, ldx >= C), lens [B]
+ * i32 on the device (clamped to 0..Tmax); rows t >= lens[b] and columns past N / C are never loaded, so nothing there
+ * (NaN included) reaches a result; lens[b] = 0 is legal; every element of dW [N][C] (ldw >= C), db [N] and sumsq is
+ * written (zeros when no row is live).  N >= 1, C a positive multiple of 8.  The f32 MFMA (v_mfma_f32_16x16x4_f32), not
+ * the split-f16 scheme: G carries the losses' 1 / sum T normalisers, i.e. f16 subnormals.  The reduction is cut into
+ * chunks of hfa_wgrad_chunk_rows() = 256 rows of one batch row, chunk (b, t / 256) whatever the grid; each chunk's f32
+ * partial of dW (a chain over its rows in ascending t) and f64 partial of db go to the workspace (hfa_wgrad_workspace_bytes(B, Tmax, N, C) bytes,
+ * 8-byte aligned, the caller's), a second pass adds the live chunks in ascending order in f64 and a third the squares in
+ * a fixed order: no float atomics, the same bits on every run and under hfa_set_grid_cap (which the first two passes
+ * honour).  Three launches, no allocation, no synchronisation.
+ *
+ * hfa_adamw_f32: one launch over the flat f32 buffers p, m (exp_avg), v (exp_avg_sq), g [n]: first the norm clip of
+ * torch.nn.utils.clip_grad_norm_ (the trainer's gradient_clip_val, train.py:139-141), g' = f32(g * f32(min(1, max_norm /
+ * (sqrt(*sumsq) + 1e-6)))) (max_norm <= 0: no clipping; g itself is not written), then one torch.optim.AdamW step
+ * (forced_alignment.py:473-486; amsgrad off): p *= 1 - lr wd; m = beta1 m + (1 - beta1) g'; v = beta2 v + (1 - beta2) g'^2;
+ * p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), each element in f64 from the f32 state and rounded once.  bc1 = 1 -
+ * beta1^step and bc2 = 1 - beta2^step come from the host, which knows the step (with OneCycleLR's cycle_momentum,
+ * forced_alignment.py:487-497, beta1 is the step's own); sumsq is the device scalar hfa_wgrad_f32 wrote, so nothing makes
+ * the host wait.  Deviation from the reference: when *sumsq is not finite the step is skipped -- p, m and v keep their
+ * bits and *skipped (i32, device) is incremented -- where clip_grad_norm_ would write NaN into every weight. */
+long long hfa_wgrad_workspace_bytes(int B, int Tmax, int N, int C);
+int hfa_wgrad_chunk_rows(void);
+int hfa_wgrad_f32(int B, int Tmax, int N, int C, const float* G, long long ldg, long long g_bs, const float* X,
+                  long long ldx, long long x_bs, const int32_t* lens, float* dW, long long ldw, float* db,
+                  double* sumsq, void* workspace, hipStream_t stream);
+int hfa_adamw_f32(long long n, float* p, float* m, float* v, const float* g, const double* sumsq, double max_norm,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, double bc1, double bc2,
+                  int32_t* skipped, hipStream_t stream);
 
 #ifdef __cplusplus
 }
